@@ -6,12 +6,17 @@ frame env%L, actions ~ U(-2,2)^28 from the counter-based generator shared with t
 full step() = RK4 mj_step-equivalent + obs + imitation reward + termination + auto-reset.
 One "step" = one dm_step over the whole batch; inputs/outputs stay resident in HBM.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0 (see the contract in the task statement) with `roofline`
-(HBM-bound accounting of the step kernel, measured live with HIP events on the launch stream)
-and `cpu_baseline` (the fp64 oracle timed on this box's host cores, rank 0, N=1 only).
+Prints ONE JSON line on rank 0 with `roofline` (HBM-bound accounting of the step kernel, measured
+live with HIP events on the launch stream during the K timed steps).  A plain run does only that:
+set up, warm up, time the K steps, print.  `--full` adds the auxiliary records, each measured in
+runs of its own after the timed steps: `physics_only`, `pipelined`, `ppo_loop`, `g1` and
+`cpu_baseline` (the fp64 oracle timed on the host cores, rank 0, N=1 only).
+`--dump-outputs DIR` writes what dm_step returned in the last timed step as DIR/<name>.npy (float32;
+with N > 1 ranks, rank r's files are DIR/rank<r>_<name>.npy).  The inputs (reset frames, generator
+seed, counter-based actions) depend only on the arguments, so two builds can be compared file by file.
 """
 import argparse
 import json
@@ -27,6 +32,25 @@ sys.path.insert(0, ROOT)
 ALGO_BYTES_PER_ENV_STEP = 1260      # 315 fp32 words of state in/out
 HBM_PEAK_GBS = 8000.0               # MI355X_MICROARCH.md: 8 TB/s spec
 EVENT_STRIDE = 4                    # every 4th launch of the timed region carries a HIP event pair
+DUMP_BYTES = 64 << 20               # --dump-outputs: at most 64 MB over all files of all ranks
+
+
+def dump_outputs(out, path, rank, world):
+    """--dump-outputs: the arrays dm_step handed its caller in the last timed step (obs, rew, done, terms, reason,
+    terminal_obs), as float32 (done / reason are small integers, exact in float32).  When they exceed this rank's share of
+    DUMP_BYTES, a fixed seeded sample of env rows is written instead, its row indices in env_index.npy."""
+    arrs = {k: v.float().cpu().numpy() for k, v in out.items()}
+    n = next(iter(arrs.values())).shape[0]
+    row_bytes = sum(a[:1].nbytes for a in arrs.values())
+    budget = DUMP_BYTES // world - 64 * 1024            # headroom for the .npy headers
+    if n * row_bytes > budget:
+        keep = np.sort(np.random.default_rng(0).choice(n, budget // (row_bytes + 8), replace=False))
+        arrs = {k: a[keep] for k, a in arrs.items()}
+        arrs["env_index"] = keep.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    prefix = "" if world == 1 else "rank%d_" % rank
+    for k, a in arrs.items():
+        np.save(os.path.join(path, prefix + k + ".npy"), np.ascontiguousarray(a))
 
 
 def _newest_pmc():
@@ -421,6 +445,11 @@ def main():
     ap.add_argument("--envs", type=int, default=4096, help="envs per GPU (BASELINE: 4096)")
     ap.add_argument("--motion", default="walk")
     ap.add_argument("--actions", default="random", choices=["random", "zero"])
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the auxiliary records (physics_only, pipelined, ppo_loop, g1, cpu_baseline); the --no-* "
+                         "options below skip single ones of them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float32, at most 64 MB in all)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-pipelined", action="store_true", help="skip the auxiliary two-sub-batch measurement (profiling runs)")
     ap.add_argument("--no-physics-only", action="store_true", help="skip the physics-only / full-step kernel comparison (profiling runs: "
@@ -563,12 +592,14 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     done_frac = float(out["done"].float().mean().item())
+    if args.dump_outputs:          # before the --full records below step the same engine into `out` again
+        dump_outputs(out, args.dump_outputs, rank, world)
 
     # SURVEY 8(d) asks for physics-only throughput beside the full step(): for `nphys` consecutive steps the pre-step state is
     # saved, dm_physics_step (the mj_step-equivalent alone: same kernel, task layer skipped, same launch order) is timed on it,
     # the state is put back and the full dm_step is timed on the SAME state.  Kernel times from the library's HIP events.
     physics_only = None
-    if args.actions == "random" and args.integrator != "Euler" and not args.no_physics_only:
+    if args.full and args.actions == "random" and args.integrator != "Euler" and not args.no_physics_only:
         nphys, tp, tf = 24, 0.0, 0.0
         eng.enable_timing(True, stride=1)
         for i in range(nphys):
@@ -594,7 +625,7 @@ def main():
     # streams with no barrier between them, as a double-buffered rollout does (policy on one half while the other
     # half simulates): the ramp-down of one launch overlaps the next launch of the other half.
     pipelined = None
-    if world == 1 and N % 2 == 0 and args.actions == "random" and not args.no_pipelined:
+    if args.full and world == 1 and N % 2 == 0 and args.actions == "random" and not args.no_pipelined:
         from deepmimic_mujoco_amd.streams import concurrent_streams
         K, n2 = 2, N // 2
         subs, sts = [], concurrent_streams(dev, 2)
@@ -625,14 +656,14 @@ def main():
             e2.close()
 
     ppo_loop = None
-    if not args.no_ppo_loop and args.actions == "random" and N == 4096 and args.integrator != "Euler":
+    if args.full and not args.no_ppo_loop and args.actions == "random" and N == 4096 and args.integrator != "Euler":
         try:
             ppo_loop = ppo_loop_record(args, dev, local_rank, rank, world, launched, barrier)
         except Exception as e:  # noqa: BLE001
             ppo_loop = {"error": repr(e)[:300]}
 
     g1 = None
-    if world == 1 and not args.no_g1 and args.actions == "random" and N == 4096 and args.integrator != "Euler":   # single-GPU runs only
+    if args.full and world == 1 and not args.no_g1 and args.actions == "random" and N == 4096 and args.integrator != "Euler":   # single-GPU runs only
         try:
             g1 = g1_record(local_rank, with_cpu=(world == 1 and not args.no_cpu_baseline))
         except Exception as e:  # noqa: BLE001
@@ -671,7 +702,7 @@ def main():
             line["pipelined"] = pipelined
         if physics_only is not None:
             line["physics_only"] = physics_only
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(model, mocap)
         print(json.dumps(line))
     eng.close()

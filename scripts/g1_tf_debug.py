@@ -1,5 +1,5 @@
-import numpy as np, torch, sys
-sys.path.insert(0,"/root/repo")
+import numpy as np, torch, os, sys
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from deepmimic_mujoco_amd.config import MotionConfig
 from deepmimic_mujoco_amd.mocap import MocapDM
 from deepmimic_mujoco_amd.g1 import G1HipEngine

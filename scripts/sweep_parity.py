@@ -1,6 +1,8 @@
 """Randomised teacher-forced parity sweep (more seeds / clips than the test suite); prints every contact-list
 mismatch that is not at the activation margin."""
-import sys; sys.path.insert(0, '/root/repo'); sys.path.insert(0, '/root/repo/tests')
+import os, sys
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'tests'))
 import numpy as np, torch
 import test_gpu_parity as T
 from deepmimic_mujoco_amd.model import load_model
