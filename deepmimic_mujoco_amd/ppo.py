@@ -675,8 +675,14 @@ class PPO:
         self._rollout_seed = (0x5EED0000 + seed + 0x9E3779B1 * self.rank) & 0x7FFFFFFFFFFFFFFF
         self.buffer_dtype = buffer_dtype
         torch.manual_seed(seed)  # identical initial weights on every rank; no parameter broadcast needed
-        self.obs_dim = int(env.observation_space.shape[0]) if env is not None else 67   # 67 DPEnv, 72 DPCombinedEnv; G1: 85 / 98
-        self.act_dim = int(env.action_space.shape[0]) if env is not None else 28        # 28 humanoid3d, 23 Unitree G1
+        if env is not None:
+            self.obs_dim = int(env.observation_space.shape[0])     # 67 DPEnv, 72 DPCombinedEnv; G1: 85 / 98
+            self.act_dim = int(env.action_space.shape[0])          # 28 humanoid3d, 23 Unitree G1
+        elif policy is not None:    # no env: the dims are the policy's (the minibatch gather and buffers are sized by them)
+            self.obs_dim = int(next(m for m in policy.pi if isinstance(m, nn.Linear)).in_features)
+            self.act_dim = int(policy.action_net.out_features)
+        else:
+            self.obs_dim, self.act_dim = 67, 28
         self.policy = (policy if policy is not None else MlpPolicy(obs_dim=self.obs_dim, act_dim=self.act_dim, net_arch=tuple(net_arch))).to(self.device)
         on_gpu = self.device.type == "cuda"
         # The optimizer step of one minibatch is ~60 small kernels: launch-bound.  On one GPU it is captured
