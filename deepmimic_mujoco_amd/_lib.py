@@ -28,7 +28,9 @@ EXPORTS = ["dm_default_config", "dm_create", "dm_destroy", "dm_last_error", "dm_
            "dm_set_clip_flags", "dm_obs_dim", "dm_terms_dim", "dm_get_env_clips", "dm_mean_step_ms", "dm_ppo_loss", "dm_forward", "dm_linear_wgrad", "dm_ppo_gather", "dm_flat_adam_step", "dm_policy_sample",
            "dm_rollout_store", "dm_policy_pack", "dm_policy_forward", "dm_policy_packed_floats", "dm_ppo_mlp_grad", "dm_ppo_mlp_workspace_floats", "dm_flat_adam_update", "dm_flat_adam_step_gather", "dm_colsum", "dm_set_seed",
            "dm_linear_tanh", "dm_tanh_linear_wgrad", "dm_tanh_bwd_colsum",
-           "dm_ppo_wide_grad", "dm_ppo_wide_packed_elems", "dm_ppo_wide_dp", "dm_ppo_wide_supported"]
+           "dm_ppo_wide_grad", "dm_ppo_wide_packed_elems", "dm_ppo_wide_dp", "dm_ppo_wide_supported",
+           "dm_sac_act", "dm_sac_store", "dm_sac_gather", "dm_sac_head_fwd", "dm_sac_critic_loss", "dm_sac_actor_loss",
+           "dm_sac_head_bwd", "dm_sac_linear_relu", "dm_sac_relu_bwd_colsum", "dm_sac_polyak"]
 
 
 class DmConfig(C.Structure):
@@ -146,6 +148,17 @@ def load_library():
     L.dm_enable_timing.argtypes = [vp, i32]
     L.dm_ppo_loss.argtypes = [vp] * 7 + [i32, i32, C.c_float, C.c_float, C.c_float, i32] + [vp] * 6
     L.dm_mean_step_ms.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_int32)]
+    u64, f32 = C.c_uint64, C.c_float
+    L.dm_sac_act.argtypes = [vp, i32, i32, i32, u64, vp, i32, i32, vp, vp, vp, vp, vp]
+    L.dm_sac_store.argtypes = [i32, i32, i32, i32] + [vp] * 17
+    L.dm_sac_gather.argtypes = [i32, i32, i32, i32, u64] + [vp] * 15
+    L.dm_sac_head_fwd.argtypes = [vp, i32, i32, i32, u64, vp, vp, vp, i32, vp, vp, i32, f32, f32, vp]
+    L.dm_sac_critic_loss.argtypes = [vp] * 5 + [i32, f32] + [vp] * 4
+    L.dm_sac_actor_loss.argtypes = [vp, vp, i32, vp, vp, vp]
+    L.dm_sac_head_bwd.argtypes = [vp, i32, i32, u64, vp, vp, i32, i32, vp, vp, vp, vp]
+    L.dm_sac_linear_relu.argtypes = [vp, i32, vp, vp, vp, i32, i32, i32, i32, vp]
+    L.dm_sac_relu_bwd_colsum.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp]
+    L.dm_sac_polyak.argtypes = [vp, vp, C.c_longlong, f32, vp, vp]
     for name in EXPORTS:
         if name not in ("dm_default_config", "dm_last_error"):
             getattr(L, name).restype = C.c_longlong if name in ("dm_policy_packed_floats", "dm_ppo_mlp_workspace_floats", "dm_ppo_wide_packed_elems") else C.c_int

@@ -17,6 +17,7 @@
 #include "dm_policy.hip"
 #include "dm_ppo_mlp.hip"
 #include "dm_ppo_wide.hip"
+#include "dm_sac.hip"
 
 struct DmEngine {
   DmConfig cfg;

@@ -1,0 +1,458 @@
+// Soft Actor-Critic (SB3 2.x SAC, as src/sac_sb3.py drives it) on the device: the rollout head, the replay ring, the minibatch
+// gather and the element-wise / reduction heads of one gradient step.  The fp32 GEMMs of the three MLPs stay on the library
+// (hipBLASLt, the reference's precision); everything between them is here, so that one gradient step is a fixed launch
+// sequence with no host read or write — the Python driver (deepmimic_mujoco_amd/sac.py) captures it once as a hipGraph.
+//
+// Device-side state the kernels share (all float / unsigned buffers owned by the caller):
+//   sac_state float[16]: [0] log_ent_coef, [1] its Adam m, [2] v, [3] step count, [4] alpha = exp(log_ent_coef) taken BEFORE the
+//                        alpha step (read by the target and both loss heads), [5] alpha loss, [6] critic loss, [7] actor loss,
+//                        [8] mean log pi of the minibatch
+//   ring unsigned[4]:    [0] write position (vec-env steps), [1] filled steps, [2] block ticket of dm_sac_store, [3] episodes done
+//   counter unsigned[1]: draw counter (rollout: bumped by dm_sac_store; learner: bumped by dm_sac_polyak)
+// Draws use the (seed, row, counter, index) hash of dm_policy_sample, so a test can restate every one of them.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+
+namespace {
+
+constexpr int SAC_THREADS = 256;
+constexpr int SAC_EP_HIST = 100;            // SB3's ep_info_buffer: deque(maxlen=100)
+constexpr unsigned SAC_GATHER_TAG = 0xFFFF0000u;
+
+__device__ __forceinline__ unsigned sac_hash32(unsigned long long seed, unsigned a, unsigned b, unsigned c) {
+  unsigned long long x = seed ^ ((unsigned long long)a * 0x9E3779B97F4A7C15ull) ^ ((unsigned long long)b * 0xBF58476D1CE4E5B9ull) ^
+                         ((unsigned long long)c * 0x94D049BB133111EBull);
+  x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull;
+  x ^= x >> 27; x *= 0x94D049BB133111EBull;
+  x ^= x >> 31;
+  return (unsigned)(x >> 32);
+}
+
+// N(0,1) pair (j, j + 1) of row r: Box-Muller exactly as ppo_sample_kernel
+__device__ __forceinline__ void sac_normal2(unsigned long long seed, unsigned r, unsigned ctr, unsigned j, float &e0, float &e1) {
+  const float u1 = ((float)(sac_hash32(seed, r, ctr, j) >> 8) + 1.0f) * (1.0f / 16777216.0f);   // (0, 1]
+  const float u2 = (float)(sac_hash32(seed, r, ctr, j + 1u) >> 8) * (1.0f / 16777216.0f);
+  const float rad = sqrtf(-2.0f * logf(u1));
+  float sn, cs;
+  sincosf(6.283185307179586f * u2, &sn, &cs);
+  e0 = rad * cs;
+  e1 = rad * sn;
+}
+
+__device__ __forceinline__ float sac_clamp_ls(float ls) { return fminf(fmaxf(ls, -20.f), 2.f); }
+
+// fixed-order block sum (256 threads): the same bits on every replay
+__device__ __forceinline__ float sac_block_sum(float v, float *red) {
+  red[threadIdx.x] = v;
+  __syncthreads();
+  for (int s = SAC_THREADS / 2; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+    __syncthreads();
+  }
+  const float t = red[0];
+  __syncthreads();
+  return t;
+}
+
+// ---- rollout head: a = tanh(mu + exp(clamp(log_std)) eps) (deterministic: tanh(mu)); act_env = lo + 0.5 (a + 1)(hi - lo).
+// Warm-up (before learning_starts): act_env uniform in [lo, hi), act = its rescaling to [-1, 1] (SB3's scale_action).
+__global__ void sac_act_kernel(const float *head, int N, int A, int ld, unsigned long long seed, const unsigned *counter, int warmup,
+                               int deterministic, const float *lo, const float *hi, float *act, float *act_env) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= N) return;
+  const unsigned ctr = counter[0];
+  for (int j = 0; j < A; j += 2) {
+    float eps[2] = {0.f, 0.f};
+    if (!warmup && !deterministic) sac_normal2(seed, (unsigned)e, ctr, (unsigned)j, eps[0], eps[1]);
+    for (int q = 0; q < 2 && j + q < A; q++) {
+      const int c = j + q;
+      const float l = lo[c], h = hi[c];
+      float a, ae;
+      if (warmup) {
+        const float u = (float)(sac_hash32(seed, (unsigned)e, ctr, (unsigned)c) >> 8) * (1.0f / 16777216.0f);   // [0, 1)
+        ae = l + u * (h - l);
+        a = 2.f * ((ae - l) / (h - l)) - 1.f;
+      } else {
+        const float mu = head[(size_t)e * ld + c];
+        a = deterministic ? tanhf(mu) : tanhf(mu + expf(sac_clamp_ls(head[(size_t)e * ld + A + c])) * eps[q]);
+        ae = l + 0.5f * (a + 1.f) * (h - l);
+      }
+      act[(size_t)e * A + c] = a;
+      act_env[(size_t)e * A + c] = ae;
+    }
+  }
+}
+
+// ---- replay ring: one row per env per vec-env step (SB3 ReplayBuffer [buffer_size // n_envs, n_envs]); next_obs of a finished
+// env is its terminal observation (SB3 _store_transition).  The last block to finish moves the ring (ticket), so every block reads
+// the position before it changes and the ring needs no host write.  Episode return / length per env; finished episodes go into a
+// 100-entry history (ep_rew_mean / ep_len_mean).
+__global__ void sac_store_kernel(int N, int D, int A, unsigned cap, const float *last_obs, const float *act, const float *rew,
+                                 const unsigned char *done, const float *obs, const float *terminal_obs, float *r_obs, float *r_act,
+                                 float *r_rew, float *r_done, float *r_next, float *last_obs_out, unsigned *ring, unsigned *counter,
+                                 float *ep_acc, float *ep_hist) {
+  __shared__ unsigned pos_s;
+  const int e = blockIdx.x;
+  if (threadIdx.x == 0) pos_s = ring[0];
+  __syncthreads();                                      // read by the block before its thread 0 takes a ticket
+  const unsigned pos = pos_s;
+  const size_t slot = (size_t)pos * N + e;
+  const bool d = done[e] != 0;
+  const float *nxt = d ? terminal_obs : obs;
+  for (int c = threadIdx.x; c < D; c += blockDim.x) {
+    const float o = obs[(size_t)e * D + c];
+    r_obs[slot * D + c] = last_obs[(size_t)e * D + c];
+    r_next[slot * D + c] = nxt[(size_t)e * D + c];
+    last_obs_out[(size_t)e * D + c] = o;
+  }
+  for (int c = threadIdx.x; c < A; c += blockDim.x) r_act[slot * A + c] = act[(size_t)e * A + c];
+  if (threadIdx.x == 0) {
+    const float r = rew[e];
+    r_rew[slot] = r;
+    r_done[slot] = d ? 1.f : 0.f;
+    float ret = ep_acc[e] + r, len = ep_acc[N + e] + 1.f;
+    if (d) {
+      const unsigned k = atomicAdd(&ring[3], 1u) % SAC_EP_HIST;
+      ep_hist[k] = ret;
+      ep_hist[SAC_EP_HIST + k] = len;
+      ret = 0.f;
+      len = 0.f;
+    }
+    ep_acc[e] = ret;
+    ep_acc[N + e] = len;
+    __threadfence();
+    if (atomicAdd(&ring[2], 1u) == (unsigned)N - 1u) {   // last block: every other block has read ring[0]
+      ring[2] = 0u;
+      ring[0] = (pos + 1u) % cap;
+      ring[1] = min(ring[1] + 1u, cap);
+      if (counter) counter[0] += 1u;
+    }
+  }
+}
+
+// ---- minibatch: B rows drawn uniformly (with replacement) over the ring[1] * N stored transitions, gathered into the layouts the
+// three networks read: obs2 [2B, D] (observations, then next observations: ONE actor pass for a_pi and a'), xq [B, D + A]
+// (obs | act: online critics), xpi [B, D + A] (obs | a_pi, the head writes a_pi), xt [B, D + A] (next_obs | a').
+__global__ void sac_gather_kernel(int B, int N, int D, int A, unsigned long long seed, const unsigned *counter, const unsigned *ring,
+                                  const float *r_obs, const float *r_act, const float *r_rew, const float *r_done, const float *r_next,
+                                  float *obs2, float *xq, float *xpi, float *xt, float *rew, float *done, int *idx_out) {
+  const int r = blockIdx.x;
+  if (r >= B) return;
+  const unsigned long long total = (unsigned long long)ring[1] * (unsigned long long)N;
+  const unsigned h = sac_hash32(seed, (unsigned)r, counter[0], SAC_GATHER_TAG);
+  const size_t i = (size_t)(((unsigned long long)h * total) >> 32);        // < total (total >= 1: the driver learns after a store)
+  const int K = D + A;
+  for (int c = threadIdx.x; c < D; c += blockDim.x) {
+    const float o = r_obs[i * D + c], n = r_next[i * D + c];
+    obs2[(size_t)r * D + c] = o;
+    obs2[(size_t)(B + r) * D + c] = n;
+    xq[(size_t)r * K + c] = o;
+    xpi[(size_t)r * K + c] = o;
+    xt[(size_t)r * K + c] = n;
+  }
+  for (int c = threadIdx.x; c < A; c += blockDim.x) xq[(size_t)r * K + D + c] = r_act[i * A + c];
+  if (threadIdx.x == 0) {
+    rew[r] = r_rew[i];
+    done[r] = r_done[i];
+    if (idx_out) idx_out[r] = (int)i;
+  }
+}
+
+// ---- squashed Gaussian head, forward, over R rows of head = [mu | log_std] (R x 2A): rows [0, Rpi) are the policy's actions on
+// obs (a_pi, written to a_pi with row stride lda), rows [Rpi, R) the next actions a' on next_obs (written to a_next).
+// log pi = sum_j log N(u_j; mu_j, std_j) - log(1 - a_j^2 + 1e-6).  One workgroup: the alpha loss -mean(log_alpha (log pi + H)),
+// its gradient and the one-scalar Adam step (torch.optim.Adam, no weight decay) ride on the reduction of the rows [0, Rpi).
+__global__ void __launch_bounds__(SAC_THREADS) sac_head_fwd_kernel(const float *head, int R, int Rpi, int A, unsigned long long seed,
+                                                                   const unsigned *counter, float *a_pi, float *a_next, int lda,
+                                                                   float *logp, float *st, int alpha_step, float target_entropy,
+                                                                   float lr, float b1, float b2, float eps_adam) {
+  __shared__ float red[SAC_THREADS];
+  const unsigned ctr = counter[0];
+  float acc = 0.f;
+  for (int r = threadIdx.x; r < R; r += SAC_THREADS) {
+    float lp = 0.f;
+    float *dst = r < Rpi ? a_pi + (size_t)r * lda : a_next + (size_t)(r - Rpi) * lda;
+    for (int j = 0; j < A; j += 2) {
+      float eps[2];
+      sac_normal2(seed, (unsigned)r, ctr, (unsigned)j, eps[0], eps[1]);
+      for (int q = 0; q < 2 && j + q < A; q++) {
+        const int c = j + q;
+        const float mu = head[(size_t)r * 2 * A + c], ls = sac_clamp_ls(head[(size_t)r * 2 * A + A + c]);
+        const float a = tanhf(mu + expf(ls) * eps[q]);
+        dst[c] = a;
+        lp += -0.5f * eps[q] * eps[q] - ls - 0.9189385332046727f - logf(1.f - a * a + 1e-6f);
+      }
+    }
+    logp[r] = lp;
+    if (r < Rpi) acc += lp;
+  }
+  const float mean_lp = sac_block_sum(acc, red) / (float)Rpi;
+  if (threadIdx.x == 0) {
+    const float la = st[0];
+    st[4] = expf(la);                                   // alpha of this gradient step (before the alpha update)
+    st[8] = mean_lp;
+    st[5] = -la * (mean_lp + target_entropy);
+    if (alpha_step) {
+      const float g = -(mean_lp + target_entropy);
+      const float t = st[3] + 1.f;
+      const float m = b1 * st[1] + (1.f - b1) * g, v = b2 * st[2] + (1.f - b2) * g * g;
+      const float bc1 = 1.f - powf(b1, t), bc2s = sqrtf(1.f - powf(b2, t));
+      st[0] = la - (lr / bc1) * m / (sqrtf(v) / bc2s + eps_adam);
+      st[1] = m; st[2] = v; st[3] = t;
+    }
+  }
+}
+
+// ---- critic target + loss: y = r + (1 - d) gamma (min_i Qt_i - alpha log pi'), loss = 0.5 sum_i mean((Q_i - y)^2);
+// dq_i = (Q_i - y) / B, db3_i = sum_b dq_i (the bias gradient of the last critic layer).  q / qt are [2, B].
+__global__ void __launch_bounds__(SAC_THREADS) sac_critic_loss_kernel(const float *q, const float *qt, const float *logp_next,
+                                                                      const float *rew, const float *done, int B, float gamma,
+                                                                      float *st, float *dq, float *db3) {
+  __shared__ float red[SAC_THREADS];
+  const float alpha = st[4], inv = 1.f / (float)B;
+  float l = 0.f, g0 = 0.f, g1 = 0.f;
+  for (int r = threadIdx.x; r < B; r += SAC_THREADS) {
+    const float nq = fminf(qt[r], qt[B + r]) - alpha * logp_next[r];
+    const float y = rew[r] + (1.f - done[r]) * gamma * nq;
+    const float e0 = q[r] - y, e1 = q[B + r] - y;
+    l += e0 * e0 + e1 * e1;
+    dq[r] = e0 * inv;
+    dq[B + r] = e1 * inv;
+    g0 += e0 * inv;
+    g1 += e1 * inv;
+  }
+  const float L = sac_block_sum(l, red), G0 = sac_block_sum(g0, red), G1 = sac_block_sum(g1, red);
+  if (threadIdx.x == 0) {
+    st[6] = 0.5f * L * inv;
+    if (db3) { db3[0] = G0; db3[1] = G1; }
+  }
+}
+
+// ---- actor loss head: mean(alpha log pi - min_i Q_i(obs, a_pi)); dq of the smaller critic (the first on a tie: torch.min) is -1/B
+__global__ void __launch_bounds__(SAC_THREADS) sac_actor_loss_kernel(const float *q, const float *logp, int B, float *st, float *dq) {
+  __shared__ float red[SAC_THREADS];
+  const float alpha = st[4], inv = 1.f / (float)B;
+  float l = 0.f;
+  for (int r = threadIdx.x; r < B; r += SAC_THREADS) {
+    const float q0 = q[r], q1 = q[B + r];
+    const bool first = q0 <= q1;
+    l += alpha * logp[r] - (first ? q0 : q1);
+    dq[r] = first ? -inv : 0.f;
+    dq[B + r] = first ? 0.f : -inv;
+  }
+  const float L = sac_block_sum(l, red);
+  if (threadIdx.x == 0) st[7] = L * inv;
+}
+
+// ---- squashed Gaussian head, backward (rows of a_pi): dL/da = dx_0[:, col:] + dx_1[:, col:] (the critics' input gradients),
+// dL/dlog pi = alpha / B.  With a = tanh(u), u = mu + std eps (eps restated from the hash, as in the forward):
+//   g_u = dL/da (1 - a^2) + alpha/B * 2 a (1 - a^2) / (1 - a^2 + 1e-6)
+//   dL/dmu = g_u,   dL/dlog_std = (g_u std eps - alpha/B) [-20 <= log_std <= 2]   (the Gaussian term's log_std derivative is -1)
+// dhead [B, 2A] = [dmu | dlog_std]; dbias [2A] = its column sums (the head's bias gradient, fixed order).
+__global__ void __launch_bounds__(SAC_THREADS) sac_head_bwd_kernel(const float *head, int B, int A, unsigned long long seed,
+                                                                   const unsigned *counter, const float *dx, int K, int col,
+                                                                   const float *st, float *dhead, float *dbias) {
+  __shared__ float red[SAC_THREADS];
+  const unsigned ctr = counter[0];
+  const float w = st[4] / (float)B;
+  for (int r = threadIdx.x; r < B; r += SAC_THREADS) {
+    for (int j = 0; j < A; j += 2) {
+      float eps[2];
+      sac_normal2(seed, (unsigned)r, ctr, (unsigned)j, eps[0], eps[1]);
+      for (int q = 0; q < 2 && j + q < A; q++) {
+        const int c = j + q;
+        const float mu = head[(size_t)r * 2 * A + c], lsr = head[(size_t)r * 2 * A + A + c], ls = sac_clamp_ls(lsr);
+        const float sd = expf(ls), a = tanhf(mu + sd * eps[q]);
+        const float da = dx[(size_t)r * K + col + c] + dx[(size_t)(B + r) * K + col + c];
+        const float om = 1.f - a * a;
+        const float gu = da * om + w * 2.f * a * om / (om + 1e-6f);
+        dhead[(size_t)r * 2 * A + c] = gu;
+        dhead[(size_t)r * 2 * A + A + c] = (lsr >= -20.f && lsr <= 2.f) ? gu * sd * eps[q] - w : 0.f;
+      }
+    }
+  }
+  __syncthreads();
+  if (dbias) {
+    // column c: 256 threads sum its B entries in a fixed order
+    for (int c = 0; c < 2 * A; c++) {
+      float s = 0.f;
+      for (int r = threadIdx.x; r < B; r += SAC_THREADS) s += dhead[(size_t)r * 2 * A + c];
+      const float t = sac_block_sum(s, red);
+      if (threadIdx.x == 0) dbias[c] = t;
+    }
+  }
+}
+
+// ---- first layer of a ReLU MLP: Y = relu(X W^T + b), X [B x I] (row stride ldx, I <= 128), W [O x I].  nets > 1 stacks that
+// many networks that read the SAME input (the twin critics): W is [nets * Onet x I] and Y is written as [nets, B, Onet], the
+// layout of the batched products of the deeper layers.  A workgroup stages 32 rows of X and 64 rows of W in LDS (odd row stride:
+// conflict-free), each thread owns 2 rows x 4 columns; bias and ReLU on the accumulators, Y written once.
+constexpr int LR_ROWS = 32, LR_COLS = 64, LR_MAXI = 128;
+__global__ void __launch_bounds__(256) sac_linear_relu_kernel(const float *__restrict__ X, int ldx, const float *__restrict__ W,
+                                                              const float *__restrict__ bias, float *__restrict__ Y, int B, int O,
+                                                              int I, int Onet) {
+  extern __shared__ float lr_lds[];
+  const int ld = I | 1;
+  float *xs = lr_lds, *ws = lr_lds + LR_ROWS * ld;
+  const int b0 = blockIdx.x * LR_ROWS, o0 = blockIdx.y * LR_COLS;
+  for (int t = threadIdx.x; t < LR_ROWS * I; t += 256) {
+    const int r = t / I, k = t - r * I;
+    xs[r * ld + k] = (b0 + r) < B ? X[(size_t)(b0 + r) * ldx + k] : 0.f;
+  }
+  for (int t = threadIdx.x; t < LR_COLS * I; t += 256) {
+    const int o = t / I, k = t - o * I;
+    ws[o * ld + k] = (o0 + o) < O ? W[(size_t)(o0 + o) * I + k] : 0.f;
+  }
+  __syncthreads();
+  const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
+  float acc[2][4];
+#pragma unroll
+  for (int i = 0; i < 2; i++)
+#pragma unroll
+    for (int u = 0; u < 4; u++) acc[i][u] = 0.f;
+  const float *x0 = xs + (2 * ty) * ld, *x1 = x0 + ld;
+  for (int k = 0; k < I; k++) {
+    const float a0 = x0[k], a1 = x1[k];
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+      const float wv = ws[(tx + 16 * u) * ld + k];
+      acc[0][u] = fmaf(a0, wv, acc[0][u]);
+      acc[1][u] = fmaf(a1, wv, acc[1][u]);
+    }
+  }
+#pragma unroll
+  for (int u = 0; u < 4; u++) {
+    const int o = o0 + tx + 16 * u;
+    if (o >= O) continue;
+    const float bb = bias[o];
+    const int net = o / Onet, oc = o - net * Onet;
+#pragma unroll
+    for (int i = 0; i < 2; i++) {
+      const int row = b0 + 2 * ty + i;
+      if (row < B) Y[((size_t)net * B + row) * Onet + oc] = fmaxf(acc[i][u] + bb, 0.f);
+    }
+  }
+}
+
+// ---- ReLU backward + bias column sum for [nets, B, O] activations: dZ = dY [Y > 0] (dZ may alias dY), db[net][o] = sum_b dZ
+// (db may be null: the actor's pass through the critics needs the input gradient only).  A workgroup owns 64 columns of one net
+// over ALL rows and reduces them in a fixed order (no float atomics): the same bits on every replay.
+__global__ void __launch_bounds__(256) sac_relu_bwd_colsum_kernel(const float *dY, const float *__restrict__ Yt, float *dZ, int B, int O,
+                                                                  float *db) {
+  __shared__ float red[4][64];
+  const int c = blockIdx.x * 64 + (threadIdx.x & 63), g = threadIdx.x >> 6, net = blockIdx.y;
+  const size_t base = (size_t)net * B * O;
+  float s = 0.f;
+  if (c < O) {
+    for (int r = g; r < B; r += 4) {
+      const size_t i = base + (size_t)r * O + c;
+      const float z = Yt[i] > 0.f ? dY[i] : 0.f;
+      dZ[i] = z;
+      s += z;
+    }
+  }
+  red[g][threadIdx.x & 63] = s;
+  __syncthreads();
+  if (db && g == 0 && c < O) db[(size_t)net * O + c] = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
+}
+
+// ---- Polyak update of the target arena (SB3 polyak_update: t *= 1 - tau; t += tau p); bumps the learner's draw counter
+__global__ void sac_polyak_kernel(const float *p, float *t, long long n, float tau, unsigned *counter) {
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    const float x = t[i] * (1.f - tau);
+    t[i] = x + tau * p[i];
+  }
+  if (counter && blockIdx.x == 0 && threadIdx.x == 0) counter[0] += 1u;
+}
+
+inline int sac_ok() { return hipGetLastError() == hipSuccess ? 0 : -5; }
+
+}  // namespace
+
+extern "C" int dm_sac_act(const float *head, int N, int A, int ld, unsigned long long seed, const unsigned *counter, int warmup,
+                          int deterministic, const float *lo, const float *hi, float *act, float *act_env, void *stream) {
+  if ((!head && !warmup) || !counter || !lo || !hi || !act || !act_env || N < 1 || A < 1 || ld < 2 * A) return -22;
+  hipLaunchKernelGGL(sac_act_kernel, dim3((N + 255) / 256), dim3(256), 0, (hipStream_t)stream, head, N, A, ld, seed, counter, warmup,
+                     deterministic, lo, hi, act, act_env);
+  return sac_ok();
+}
+
+extern "C" int dm_sac_store(int N, int D, int A, int cap_steps, const float *last_obs, const float *act, const float *rew,
+                            const unsigned char *done, const float *obs, const float *terminal_obs, float *r_obs, float *r_act,
+                            float *r_rew, float *r_done, float *r_next, float *last_obs_out, unsigned *ring, unsigned *counter,
+                            float *ep_acc, float *ep_hist, void *stream) {
+  if (N < 1 || D < 1 || A < 1 || cap_steps < 1 || !last_obs || !act || !rew || !done || !obs || !terminal_obs || !r_obs || !r_act ||
+      !r_rew || !r_done || !r_next || !last_obs_out || !ring || !ep_acc || !ep_hist)
+    return -22;
+  hipLaunchKernelGGL(sac_store_kernel, dim3(N), dim3(64), 0, (hipStream_t)stream, N, D, A, (unsigned)cap_steps, last_obs, act, rew, done,
+                     obs, terminal_obs, r_obs, r_act, r_rew, r_done, r_next, last_obs_out, ring, counter, ep_acc, ep_hist);
+  return sac_ok();
+}
+
+extern "C" int dm_sac_gather(int B, int N, int D, int A, unsigned long long seed, const unsigned *counter, const unsigned *ring,
+                             const float *r_obs, const float *r_act, const float *r_rew, const float *r_done, const float *r_next,
+                             float *obs2, float *xq, float *xpi, float *xt, float *rew, float *done, int *idx_out, void *stream) {
+  if (B < 1 || N < 1 || D < 1 || A < 1 || !counter || !ring || !r_obs || !r_act || !r_rew || !r_done || !r_next || !obs2 || !xq ||
+      !xpi || !xt || !rew || !done)
+    return -22;
+  hipLaunchKernelGGL(sac_gather_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, B, N, D, A, seed, counter, ring, r_obs, r_act, r_rew,
+                     r_done, r_next, obs2, xq, xpi, xt, rew, done, idx_out);
+  return sac_ok();
+}
+
+extern "C" int dm_sac_head_fwd(const float *head, int R, int Rpi, int A, unsigned long long seed, const unsigned *counter, float *a_pi,
+                               float *a_next, int lda, float *logp, float *sac_state, int alpha_step, float target_entropy, float lr,
+                               void *stream) {
+  if (!head || R < 1 || Rpi < 1 || Rpi > R || A < 1 || !counter || !a_pi || (R > Rpi && !a_next) || lda < A || !logp || !sac_state)
+    return -22;
+  hipLaunchKernelGGL(sac_head_fwd_kernel, dim3(1), dim3(SAC_THREADS), 0, (hipStream_t)stream, head, R, Rpi, A, seed, counter, a_pi,
+                     a_next, lda, logp, sac_state, alpha_step, target_entropy, lr, 0.9f, 0.999f, 1e-8f);
+  return sac_ok();
+}
+
+extern "C" int dm_sac_critic_loss(const float *q, const float *qt, const float *logp_next, const float *rew, const float *done, int B,
+                                  float gamma, float *sac_state, float *dq, float *db3, void *stream) {
+  if (!q || !qt || !logp_next || !rew || !done || B < 1 || !sac_state || !dq) return -22;
+  hipLaunchKernelGGL(sac_critic_loss_kernel, dim3(1), dim3(SAC_THREADS), 0, (hipStream_t)stream, q, qt, logp_next, rew, done, B, gamma,
+                     sac_state, dq, db3);
+  return sac_ok();
+}
+
+extern "C" int dm_sac_actor_loss(const float *q, const float *logp, int B, float *sac_state, float *dq, void *stream) {
+  if (!q || !logp || B < 1 || !sac_state || !dq) return -22;
+  hipLaunchKernelGGL(sac_actor_loss_kernel, dim3(1), dim3(SAC_THREADS), 0, (hipStream_t)stream, q, logp, B, sac_state, dq);
+  return sac_ok();
+}
+
+extern "C" int dm_sac_head_bwd(const float *head, int B, int A, unsigned long long seed, const unsigned *counter, const float *dx, int K,
+                               int col, const float *sac_state, float *dhead, float *dbias, void *stream) {
+  if (!head || B < 1 || A < 1 || !counter || !dx || col < 0 || col + A > K || !sac_state || !dhead) return -22;
+  hipLaunchKernelGGL(sac_head_bwd_kernel, dim3(1), dim3(SAC_THREADS), 0, (hipStream_t)stream, head, B, A, seed, counter, dx, K, col,
+                     sac_state, dhead, dbias);
+  return sac_ok();
+}
+
+extern "C" int dm_sac_linear_relu(const float *X, int ldx, const float *W, const float *bias, float *Y, int B, int O, int I, int nets,
+                                  void *stream) {
+  if (!X || !W || !bias || !Y || B < 1 || O < 1 || I < 1 || I > LR_MAXI || ldx < I || nets < 1 || O % nets) return -22;
+  const size_t lds = (size_t)(LR_ROWS + LR_COLS) * (I | 1) * sizeof(float);   // <= 49.5 KB at I = 128
+  hipLaunchKernelGGL(sac_linear_relu_kernel, dim3((B + LR_ROWS - 1) / LR_ROWS, (O + LR_COLS - 1) / LR_COLS), dim3(256), lds,
+                     (hipStream_t)stream, X, ldx, W, bias, Y, B, O, I, O / nets);
+  return sac_ok();
+}
+
+extern "C" int dm_sac_relu_bwd_colsum(const float *dY, const float *Y, float *dZ, float *db, int B, int O, int nets, void *stream) {
+  if (!dY || !Y || !dZ || B < 1 || O < 1 || nets < 1) return -22;
+  hipLaunchKernelGGL(sac_relu_bwd_colsum_kernel, dim3((O + 63) / 64, nets), dim3(256), 0, (hipStream_t)stream, dY, Y, dZ, B, O, db);
+  return sac_ok();
+}
+
+extern "C" int dm_sac_polyak(const float *p, float *t, long long n, float tau, unsigned *counter, void *stream) {
+  if (!p || !t || n < 1) return -22;
+  long long blocks = (n + 256 * 4 - 1) / (256 * 4);
+  if (blocks > 1024) blocks = 1024;
+  hipLaunchKernelGGL(sac_polyak_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, t, n, tau, counter);
+  return sac_ok();
+}

@@ -2,6 +2,7 @@
 
     python -m deepmimic_mujoco_amd.train --motion walk --envs 4096 --horizon 32 --total 2000000
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 -m deepmimic_mujoco_amd.train ...
+    python -m deepmimic_mujoco_amd.train --algo sac --motion getup_facedown --arch 1024,512 --envs 32   (src/sac_sb3.py)
 
 One process per GPU; every rank owns `--envs` environments (sharded, no collective on the env path)
 and a policy replica; gradients are all-reduced once per optimizer step (RCCL over xGMI).
@@ -17,6 +18,10 @@ import torch.distributed as dist
 
 def main(argv=None):
     ap = argparse.ArgumentParser()
+    ap.add_argument("--algo", default="ppo", choices=["ppo", "sac"], help="sac: SB3 SAC of src/sac_sb3.py (one GPU, sac.py)")
+    ap.add_argument("--buffer-size", type=int, default=5_000_000, help="--algo sac: replay transitions (src/sac_sb3.py)")
+    ap.add_argument("--learning-starts", type=int, default=100, help="--algo sac: uniform-action env steps before learning")
+    ap.add_argument("--gradient-steps", type=int, default=1, help="--algo sac: gradient steps per vec-env step")
     ap.add_argument("--motion", default="walk", help="clip name or comma list (multi-clip: env i -> clip i mod k)")
     ap.add_argument("--env", default="deep_mimic_mujoco", choices=["deep_mimic_mujoco", "dp_combined_env"],
                     help="env_name of src/sb3_ppo.py:247-248 (dp_combined_env: walk/run/getup state machine on humanoid3d)")
@@ -48,6 +53,8 @@ def main(argv=None):
     args = ap.parse_args(argv)
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
+    if args.algo == "sac" and world > 1:
+        ap.error("--algo sac runs one learner on one GPU (SB3's SAC has no data-parallel mode): launch it without torch.distributed")
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     if world > 1:
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
@@ -73,6 +80,8 @@ def main(argv=None):
     else:
         env = HipDeepMimicVecEnv(args.envs, motion=motions if len(motions) > 1 else motions[0], device=local_rank,
                                  seed=1234 + 7919 * rank, sub_batches=sb)
+    if args.algo == "sac":
+        return _train_sac(args, env, motions, local_rank)
     ppo = PPO(env, net_arch=tuple(int(x) for x in args.arch.split(",")), n_steps=args.horizon,
               batch_size=args.minibatch, n_epochs=args.epochs, learning_rate=args.lr, seed=args.seed,
               buffer_dtype=torch.bfloat16 if args.bf16_buffer else torch.float32, rollout_graph=args.rollout_graph,
@@ -115,6 +124,49 @@ def main(argv=None):
     env.close()
     if world > 1:
         dist.destroy_process_group()
+
+
+def _train_sac(args, env, motions, local_rank):
+    """src/sac_sb3.py: SAC(MlpPolicy, net_arch=[1024, 512] by --arch, buffer_size) with SB3's other defaults; one learner."""
+    from .sac import SAC
+    sac = SAC(env, net_arch=tuple(int(x) for x in args.arch.split(",")), buffer_size=args.buffer_size,
+              learning_starts=args.learning_starts, gradient_steps=args.gradient_steps, seed=args.seed)
+    hist = []
+    dash = None
+    if args.eval_every > 0:
+        from .eval_dashboard import EvalDashboardCallback
+        if args.env == "dp_combined_env":
+            from .combined_env import DPCombinedEnv
+            eval_env = DPCombinedEnv(robot=args.robot, device=local_rank)
+        else:
+            from .deepmimic_env import DPEnv
+            eval_env = DPEnv(motions[0], robot=args.robot, device=local_rank)
+        dash = EvalDashboardCallback(eval_env, args.motion + "_" + args.run_name, every_n_global_steps=args.eval_every, out_root=args.eval_dir)
+
+    def _cb(m):
+        hist.append(dict(m.stats))
+        if not args.json:
+            print("steps %(total_timesteps)d  ep_rew_mean %(ep_rew_mean).3f  ep_len_mean %(ep_len_mean).1f  critic %(critic_loss).4f  "
+                  "actor %(actor_loss).4f  ent_coef %(ent_coef).4f  fps %(fps).0f" % m.stats, flush=True)
+        if dash is not None:
+            dash(m)
+        return True
+    t0 = time.perf_counter()
+    # stats (one synchronisation) every ~100 k transitions: the loop in between never waits for the device
+    sac.learn(args.total, callback=_cb, log_interval=max(1, 100_000 // env.num_envs))
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    if args.save:
+        sac.save(os.path.expanduser(args.save))
+    if args.json:
+        last = hist[-1] if hist else {}
+        print(json.dumps({"workload": "sac", "envs": env.num_envs, "arch": args.arch, "buffer_size": args.buffer_size,
+                          "gradient_steps": args.gradient_steps, "total_timesteps": sac.num_timesteps, "n_updates": sac._n_updates,
+                          "env_steps_per_s": sac.num_timesteps / dt, "wall_s": dt,
+                          "ep_rew_mean": last.get("ep_rew_mean"), "ep_len_mean": last.get("ep_len_mean"),
+                          "critic_loss": last.get("critic_loss"), "actor_loss": last.get("actor_loss"), "ent_coef": last.get("ent_coef"),
+                          "curve": [(h["total_timesteps"], h["ep_rew_mean"]) for h in hist[::max(1, len(hist) // 200)]]}))
+    env.close()
 
 
 if __name__ == "__main__":

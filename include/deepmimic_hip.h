@@ -338,6 +338,47 @@ int dm_ppo_wide_dp(int D);
 int dm_ppo_wide_supported(int B, int D, int H1, int H2, int A);
 int dm_ppo_wide_grad(const DmPpoWideStep *step, void *stream);
 
+/* Soft Actor-Critic (SB3 2.x SAC as src/sac_sb3.py drives it [EXT]) around the library GEMMs (csrc/dm_sac.hip).  Device state:
+ * sac_state float[16] ({log_ent_coef, its Adam m, v, step, alpha of the step, alpha / critic / actor loss, mean log pi, ...}),
+ * ring uint32[4] ({write position, filled vec-env steps, block ticket, finished episodes}), draw counters uint32[1].  Draws are
+ * the (seed, row, counter, index) hash of dm_policy_sample.
+ * dm_sac_act: rollout head over head = [mu | log_std] (row stride ld): act = tanh(mu + exp(clamp(log_std, -20, 2)) eps) in [-1, 1],
+ *   act_env = lo + 0.5 (act + 1)(hi - lo); warmup != 0: act_env uniform in [lo, hi), act its rescaling (head unused).
+ * dm_sac_store: replay-ring row per env (obs, act, rew, done, next_obs = done ? terminal_obs : obs), last_obs_out <- obs, ring and
+ *   counter advanced on the device; ep_acc float[2N] (return, length per env), ep_hist float[200] (last 100 episodes).
+ * dm_sac_gather: B transitions uniform over the stored ones into obs2 [2B x D] (obs, next_obs), xq (obs | act), xpi (obs | .),
+ *   xt (next_obs | .) [B x (D + A)], rew, done; idx_out (optional) the ring rows.
+ * dm_sac_head_fwd: squashed Gaussian over R rows of head [R x 2A]: a (rows < Rpi to a_pi, the rest to a_next, row stride lda),
+ *   logp [R]; alpha of the step -> sac_state[4], alpha loss of the rows < Rpi and (alpha_step) the log_ent_coef Adam step.
+ * dm_sac_critic_loss: y = r + (1 - d) gamma (min Qt - alpha logp'), dq [2 x B] of 0.5 sum_i mse(Q_i, y), db3[2] its sums.
+ * dm_sac_actor_loss: dq [2 x B] of mean(alpha logp - min_i Q_i) (the first critic on a tie).
+ * dm_sac_head_bwd: dhead [B x 2A] from dL/da = dx[0][:, col:] + dx[1][:, col:] (dx [2 x B x K]) and dL/dlogp = alpha / B;
+ *   dbias[2A] its column sums.
+ * dm_sac_linear_relu: Y = relu(X W^T + b) (X [B x I], row stride ldx, I <= 128; W [O x I]) written as [nets, B, O / nets].
+ * dm_sac_relu_bwd_colsum: dZ = dY [Y > 0] over [nets, B, O] (dZ may alias dY), db [nets x O] = column sums (db may be NULL).
+ * dm_sac_polyak: t = t (1 - tau) + tau p over n floats; counter[0] += 1 (may be NULL). */
+int dm_sac_act(const float *head, int N, int A, int ld, unsigned long long seed, const unsigned *counter, int warmup,
+               int deterministic, const float *lo, const float *hi, float *act, float *act_env, void *stream);
+int dm_sac_store(int N, int D, int A, int cap_steps, const float *last_obs, const float *act, const float *rew,
+                 const uint8_t *done, const float *obs, const float *terminal_obs, float *r_obs, float *r_act, float *r_rew,
+                 float *r_done, float *r_next, float *last_obs_out, unsigned *ring, unsigned *counter, float *ep_acc,
+                 float *ep_hist, void *stream);
+int dm_sac_gather(int B, int N, int D, int A, unsigned long long seed, const unsigned *counter, const unsigned *ring,
+                  const float *r_obs, const float *r_act, const float *r_rew, const float *r_done, const float *r_next,
+                  float *obs2, float *xq, float *xpi, float *xt, float *rew, float *done, int *idx_out, void *stream);
+int dm_sac_head_fwd(const float *head, int R, int Rpi, int A, unsigned long long seed, const unsigned *counter, float *a_pi,
+                    float *a_next, int lda, float *logp, float *sac_state, int alpha_step, float target_entropy, float lr,
+                    void *stream);
+int dm_sac_critic_loss(const float *q, const float *qt, const float *logp_next, const float *rew, const float *done, int B,
+                       float gamma, float *sac_state, float *dq, float *db3, void *stream);
+int dm_sac_actor_loss(const float *q, const float *logp, int B, float *sac_state, float *dq, void *stream);
+int dm_sac_head_bwd(const float *head, int B, int A, unsigned long long seed, const unsigned *counter, const float *dx, int K,
+                    int col, const float *sac_state, float *dhead, float *dbias, void *stream);
+int dm_sac_linear_relu(const float *X, int ldx, const float *W, const float *bias, float *Y, int B, int O, int I, int nets,
+                       void *stream);
+int dm_sac_relu_bwd_colsum(const float *dY, const float *Y, float *dZ, float *db, int B, int O, int nets, void *stream);
+int dm_sac_polyak(const float *p, float *t, long long n, float tau, unsigned *counter, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
