@@ -30,7 +30,8 @@ EXPORTS = ["dm_default_config", "dm_create", "dm_destroy", "dm_last_error", "dm_
            "dm_linear_tanh", "dm_tanh_linear_wgrad", "dm_tanh_bwd_colsum",
            "dm_ppo_wide_grad", "dm_ppo_wide_packed_elems", "dm_ppo_wide_dp", "dm_ppo_wide_supported",
            "dm_sac_act", "dm_sac_store", "dm_sac_gather", "dm_sac_head_fwd", "dm_sac_critic_loss", "dm_sac_actor_loss",
-           "dm_sac_head_bwd", "dm_sac_linear_relu", "dm_sac_relu_bwd_colsum", "dm_sac_polyak"]
+           "dm_sac_head_bwd", "dm_sac_linear_relu", "dm_sac_relu_bwd_colsum", "dm_sac_polyak",
+           "dm_rollout_finish", "dm_rollout_finish_workspace_bytes"]
 
 
 class DmConfig(C.Structure):
@@ -159,9 +160,11 @@ def load_library():
     L.dm_sac_linear_relu.argtypes = [vp, i32, vp, vp, vp, i32, i32, i32, i32, vp]
     L.dm_sac_relu_bwd_colsum.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp]
     L.dm_sac_polyak.argtypes = [vp, vp, C.c_longlong, f32, vp, vp]
+    L.dm_rollout_finish_workspace_bytes.argtypes = [i32, i32]
+    L.dm_rollout_finish.argtypes = [i32, i32, vp, vp, i32, vp, vp, C.c_double, C.c_double] + [vp] * 7 + [C.c_longlong, vp]
     for name in EXPORTS:
         if name not in ("dm_default_config", "dm_last_error"):
-            getattr(L, name).restype = C.c_longlong if name in ("dm_policy_packed_floats", "dm_ppo_mlp_workspace_floats", "dm_ppo_wide_packed_elems") else C.c_int
+            getattr(L, name).restype = C.c_longlong if name in ("dm_policy_packed_floats", "dm_ppo_mlp_workspace_floats", "dm_ppo_wide_packed_elems", "dm_rollout_finish_workspace_bytes") else C.c_int
     _LIB = L
     return L
 

@@ -818,3 +818,270 @@ extern "C" int dm_rollout_store(int N, int D, int A, const float *last_obs, cons
                      b_obs, b_act, b_val, b_logp, b_rew, b_done, last_obs_out, counter);
   return hipGetLastError() == hipSuccess ? 0 : -5;
 }
+
+// ---- dm_rollout_finish: what follows the T env steps of a rollout, as one call — SB3's RolloutBuffer.compute_returns_and_advantage
+// (GAE), the vec-env Monitor (episode return / length, history of the last 100 finished episodes) and the rollout statistics.
+// One thread per env column (loads coalesced across envs), serial in t: the dependent chain per step is one multiply and one add,
+// the loads do not depend on it.  Three launches on the caller's stream:
+//   rollout_gae_kernel      backward scan: adv / ret; per (step, block) the number of finished episodes; per block the fp64 partials
+//   rollout_rank_kernel     one block: exclusive scan of those counts in (step, block) order = the number of every block's first
+//                           episode of a step; fixed-order merge of the partials -> stats; ep_count += episodes of this call
+//   rollout_monitor_kernel  forward scan: running return / length per env; the episode that ends at (t, env) is number
+//                           count0 + base[t][block] + (finished lanes below it in the wave) and goes to slot (number mod 100)
+// No atomics: every number above is a function of the inputs alone, so two runs give the same bits.
+namespace {
+
+constexpr int RF_BLOCK = 64;          // one wave per block: the in-step order of finished episodes is a ballot
+constexpr int RF_HIST = 100;          // SB3: ep_info_buffer = deque(maxlen=100)
+constexpr int RF_PART = 8;            // doubles per block: n, mean(ret), M2(ret), mean(ret - val), M2(ret - val), sum(rew), dones, -
+constexpr int RF_SCAN = 1024;
+constexpr int RF_U = 16;             // steps per group of loads
+
+struct RfMoments { double n, mean, m2; };
+
+// Chan et al.: moments of the union of two samples; symmetric in (a, b), so both sides of a butterfly get the same bits, and
+// exact for a constant sample (delta = 0 -> M2 = 0), which is what makes var(ret) = 0 come out as 0 and not as rounding noise
+__device__ __forceinline__ RfMoments rf_merge(RfMoments a, RfMoments b) {
+  if (a.n == 0.0) return b;
+  if (b.n == 0.0) return a;
+  const double n = a.n + b.n;
+  const double d = b.mean - a.mean;
+  RfMoments r;
+  r.n = n;
+  r.mean = d == 0.0 ? a.mean : (a.n * a.mean + b.n * b.mean) / n;
+  r.m2 = (a.m2 + b.m2) + d * d * (a.n * b.n / n);
+  return r;
+}
+
+__device__ __forceinline__ RfMoments rf_wave_merge(RfMoments m) {
+  for (int o = 32; o > 0; o >>= 1) {
+    RfMoments p{__shfl_xor(m.n, o), __shfl_xor(m.mean, o), __shfl_xor(m.m2, o)};
+    m = rf_merge(m, p);
+  }
+  return m;
+}
+
+__device__ __forceinline__ double rf_wave_sum(double v) {
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+
+// shifted sums of one column (shift = its first value) -> moments
+__device__ __forceinline__ RfMoments rf_column(double n, double shift, double s1, double s2) {
+  RfMoments m;
+  m.n = n;
+  m.mean = n > 0.0 ? shift + s1 / n : 0.0;
+  m.m2 = n > 0.0 ? fmax(s2 - s1 * s1 / n, 0.0) : 0.0;
+  return m;
+}
+
+// Steps are taken RF_U at a time: the loads of the next group are issued before the current group's chain is evaluated (no load
+// sits behind a branch on a run-time condition; lanes past N read column N - 1 and store nothing), so the wave waits for memory
+// once per group and never per step.
+template <typename DoneT>
+__global__ void __launch_bounds__(RF_BLOCK) rollout_gae_kernel(int T, int N, const float *__restrict__ rew, const DoneT *__restrict__ done,
+                                                               const float *__restrict__ val, const float *__restrict__ last_val, float g,
+                                                               float gl, float *__restrict__ adv, float *__restrict__ ret,
+                                                               const unsigned *__restrict__ ep_count, unsigned *__restrict__ head,
+                                                               unsigned *__restrict__ cnt, double *__restrict__ part) {
+#pragma clang fp contract(off)        // every operation rounds to fp32 on its own, as the elementwise kernels of compute_gae do
+  const int e = blockIdx.x * RF_BLOCK + threadIdx.x;
+  const bool live = e < N;
+  const int ec = live ? e : N - 1;
+  const int nb = gridDim.x;
+  if (blockIdx.x == 0 && threadIdx.x == 0) head[0] = ep_count[0];        // the monitor kernel numbers episodes from here
+  float next_v = last_val[ec], last = 0.f;
+  double ky = 0.0, kd = 0.0, sy = 0.0, syy = 0.0, sd = 0.0, sdd = 0.0, sr = 0.0, nd = 0.0;
+  float r[RF_U], d[RF_U], v[RF_U], rn[RF_U], dn[RF_U], vn[RF_U];
+#pragma unroll
+  for (int k = 0; k < RF_U; k++) {
+    const size_t i = (size_t)max(T - 1 - k, 0) * N + ec;
+    r[k] = rew[i]; d[k] = (float)done[i]; v[k] = val[i];
+  }
+  for (int t0 = T - 1; t0 >= 0; t0 -= RF_U) {
+#pragma unroll
+    for (int k = 0; k < RF_U; k++) {                                     // the next group (clamped at step 0: read, not used)
+      const size_t i = (size_t)max(t0 - RF_U - k, 0) * N + ec;
+      rn[k] = rew[i]; dn[k] = (float)done[i]; vn[k] = val[i];
+    }
+#pragma unroll
+    for (int k = 0; k < RF_U; k++) {
+      const int t = t0 - k;
+      if (t >= 0) {
+        const size_t i = (size_t)t * N + ec;
+        const float nt = 1.0f - d[k];
+        const float gv = g * next_v;
+        const float bootstrap = gv * nt;
+        const float target = r[k] + bootstrap;
+        const float delta = target - v[k];
+        const float carry = gl * nt;
+        const float decayed = carry * last;
+        last = delta + decayed;
+        const float rt = last + v[k];
+        next_v = v[k];
+        const bool fin = live && d[k] != 0.f;
+        const unsigned long long m = __ballot(fin);
+        if (threadIdx.x == 0) cnt[(size_t)t * nb + blockIdx.x] = (unsigned)__popcll(m);
+        if (live) {
+          adv[i] = last;
+          ret[i] = rt;
+        }
+        const double y = (double)rt, dv = (double)rt - (double)v[k];
+        if (t == T - 1) { ky = y; kd = dv; }
+        sy += y - ky; syy += (y - ky) * (y - ky);
+        sd += dv - kd; sdd += (dv - kd) * (dv - kd);
+        sr += (double)r[k];
+        nd += fin ? 1.0 : 0.0;
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < RF_U; k++) { r[k] = rn[k]; d[k] = dn[k]; v[k] = vn[k]; }
+  }
+  const double n = live ? (double)T : 0.0;
+  const RfMoments my = rf_wave_merge(rf_column(n, ky, sy, syy));
+  const RfMoments md = rf_wave_merge(rf_column(n, kd, sd, sdd));
+  sr = rf_wave_sum(live ? sr : 0.0);
+  nd = rf_wave_sum(nd);
+  if (threadIdx.x == 0) {
+    double *p = part + (size_t)blockIdx.x * RF_PART;
+    p[0] = my.n; p[1] = my.mean; p[2] = my.m2; p[3] = md.mean; p[4] = md.m2; p[5] = sr; p[6] = nd; p[7] = 0.0;
+  }
+}
+
+// stats: [0] sum of rewards, [1] finished episodes in this rollout, [2] explained variance, [3] var(ret), [4] var(ret - val),
+// [5] T * N, [6] episodes finished so far (ep_count after this call), [7] mean(ret)
+__global__ void __launch_bounds__(RF_SCAN) rollout_rank_kernel(int M, int nb, unsigned *__restrict__ cnt, const double *__restrict__ part,
+                                                               unsigned *__restrict__ head, unsigned *__restrict__ ep_count,
+                                                               double *__restrict__ stats) {
+  __shared__ unsigned sums[RF_SCAN];
+  const int tid = threadIdx.x;
+  const int chunk = (M + RF_SCAN - 1) / RF_SCAN;
+  const int lo = min(tid * chunk, M), hi = min(lo + chunk, M);
+  unsigned s = 0;
+  for (int i = lo; i < hi; i++) s += cnt[i];
+  sums[tid] = s;
+  __syncthreads();
+  for (int o = 1; o < RF_SCAN; o <<= 1) {            // Hillis-Steele inclusive scan of the per-thread totals (integers: exact)
+    const unsigned add = tid >= o ? sums[tid - o] : 0u;
+    __syncthreads();
+    sums[tid] += add;
+    __syncthreads();
+  }
+  unsigned run = tid > 0 ? sums[tid - 1] : 0u;
+  for (int i = lo; i < hi; i++) { const unsigned c = cnt[i]; cnt[i] = run; run += c; }
+  const unsigned total = sums[RF_SCAN - 1];
+  if (tid == 0) {
+    head[1] = total;
+    ep_count[0] = head[0] + total;
+  }
+  if (tid < 64) {                                    // first wave: block partials, lane l takes blocks l, l + 64, ... in order
+    RfMoments my{0.0, 0.0, 0.0}, md{0.0, 0.0, 0.0};
+    double sr = 0.0, nd = 0.0;
+    for (int b = tid; b < nb; b += 64) {
+      const double *p = part + (size_t)b * RF_PART;
+      my = rf_merge(my, RfMoments{p[0], p[1], p[2]});
+      md = rf_merge(md, RfMoments{p[0], p[3], p[4]});
+      sr += p[5];
+      nd += p[6];
+    }
+    my = rf_wave_merge(my);
+    md = rf_wave_merge(md);
+    sr = rf_wave_sum(sr);
+    nd = rf_wave_sum(nd);
+    if (tid == 0) {
+      const double vy = my.m2 / my.n, vd = md.m2 / md.n;
+      stats[0] = sr; stats[1] = nd;
+      stats[2] = vy == 0.0 ? __longlong_as_double(0x7ff8000000000000LL) : 1.0 - vd / vy;
+      stats[3] = vy; stats[4] = vd; stats[5] = my.n; stats[6] = (double)(head[0] + total); stats[7] = my.mean;
+    }
+  }
+}
+
+template <typename DoneT>
+__global__ void __launch_bounds__(RF_BLOCK) rollout_monitor_kernel(int T, int N, const float *__restrict__ rew, const DoneT *__restrict__ done,
+                                                                   const unsigned *__restrict__ base, const unsigned *__restrict__ head,
+                                                                   float *__restrict__ ep_acc, float *__restrict__ ep_hist) {
+#pragma clang fp contract(off)
+  const int e = blockIdx.x * RF_BLOCK + threadIdx.x;
+  const bool live = e < N;
+  const int ec = live ? e : N - 1;
+  const int nb = gridDim.x;
+  const unsigned count0 = head[0], total = head[1];
+  const unsigned long long below = (1ull << threadIdx.x) - 1ull;
+  float er = ep_acc[ec], el = ep_acc[N + ec];
+  float r[RF_U], rn[RF_U];
+  bool f[RF_U], fn[RF_U];
+  unsigned first[RF_U], firstn[RF_U];
+#pragma unroll
+  for (int k = 0; k < RF_U; k++) {
+    const int t = min(k, T - 1);
+    r[k] = rew[(size_t)t * N + ec]; f[k] = done[(size_t)t * N + ec] != (DoneT)0; first[k] = base[(size_t)t * nb + blockIdx.x];
+  }
+  for (int t0 = 0; t0 < T; t0 += RF_U) {
+#pragma unroll
+    for (int k = 0; k < RF_U; k++) {
+      const int t = min(t0 + RF_U + k, T - 1);
+      rn[k] = rew[(size_t)t * N + ec]; fn[k] = done[(size_t)t * N + ec] != (DoneT)0; firstn[k] = base[(size_t)t * nb + blockIdx.x];
+    }
+#pragma unroll
+    for (int k = 0; k < RF_U; k++) {
+      if (t0 + k < T) {
+        const bool fin = live && f[k];
+        const unsigned long long m = __ballot(fin);
+        er += r[k];
+        el += 1.0f;
+        if (fin) {
+          const unsigned j = first[k] + (unsigned)__popcll(m & below);     // number of this episode within the call
+          if (j + (unsigned)RF_HIST >= total) {                            // one of the last 100: their slots are distinct
+            const unsigned s = (unsigned)(((unsigned long long)count0 + j) % (unsigned)RF_HIST);
+            ep_hist[s] = er;
+            ep_hist[RF_HIST + s] = el;
+          }
+          er = 0.f;
+          el = 0.f;
+        }
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < RF_U; k++) { r[k] = rn[k]; f[k] = fn[k]; first[k] = firstn[k]; }
+  }
+  if (live) { ep_acc[e] = er; ep_acc[N + e] = el; }
+}
+
+}  // namespace
+
+extern "C" long long dm_rollout_finish_workspace_bytes(int T, int N) {
+  if (T < 1 || N < 1) return -22;
+  const long long nb = (N + RF_BLOCK - 1) / RF_BLOCK;
+  return 16 + nb * RF_PART * 8 + (long long)T * nb * 4;                    // head (padded to 16) | block partials | counts
+}
+
+extern "C" int dm_rollout_finish(int T, int N, const float *rew, const void *done, int done_is_u8, const float *val,
+                                 const float *last_val, double gamma, double gae_lambda, float *adv, float *ret, float *ep_acc,
+                                 float *ep_hist, unsigned *ep_count, double *stats, void *work, long long work_bytes, void *stream) {
+  if (T < 1 || N < 1 || !rew || !done || !val || !last_val || !adv || !ret || !ep_acc || !ep_hist || !ep_count || !stats || !work)
+    return -22;
+  if ((long long)T * ((N + RF_BLOCK - 1) / RF_BLOCK) > 0x7fffffffLL || ((uintptr_t)work & 15) ||
+      work_bytes < dm_rollout_finish_workspace_bytes(T, N))
+    return -22;
+  const int nb = (N + RF_BLOCK - 1) / RF_BLOCK;
+  unsigned *head = (unsigned *)work;
+  double *part = (double *)((char *)work + 16);
+  unsigned *cnt = (unsigned *)((char *)work + 16 + (size_t)nb * RF_PART * 8);
+  const float g = (float)gamma, gl = (float)(gamma * gae_lambda);          // the product in double, as Python takes it
+  hipStream_t s = (hipStream_t)stream;
+  if (done_is_u8)
+    hipLaunchKernelGGL(rollout_gae_kernel<unsigned char>, dim3(nb), dim3(RF_BLOCK), 0, s, T, N, rew, (const unsigned char *)done, val,
+                       last_val, g, gl, adv, ret, ep_count, head, cnt, part);
+  else
+    hipLaunchKernelGGL(rollout_gae_kernel<float>, dim3(nb), dim3(RF_BLOCK), 0, s, T, N, rew, (const float *)done, val, last_val, g, gl,
+                       adv, ret, ep_count, head, cnt, part);
+  hipLaunchKernelGGL(rollout_rank_kernel, dim3(1), dim3(RF_SCAN), 0, s, T * nb, nb, cnt, part, head, ep_count, stats);
+  if (done_is_u8)
+    hipLaunchKernelGGL(rollout_monitor_kernel<unsigned char>, dim3(nb), dim3(RF_BLOCK), 0, s, T, N, rew, (const unsigned char *)done, cnt,
+                       head, ep_acc, ep_hist);
+  else
+    hipLaunchKernelGGL(rollout_monitor_kernel<float>, dim3(nb), dim3(RF_BLOCK), 0, s, T, N, rew, (const float *)done, cnt, head, ep_acc,
+                       ep_hist);
+  return hipGetLastError() == hipSuccess ? 0 : -5;
+}

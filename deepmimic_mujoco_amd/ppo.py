@@ -502,6 +502,117 @@ def compute_gae(rewards, values, dones, last_values, gamma, lam):
     return adv, adv + values
 
 
+EP_HIST = 100        # SB3: ep_info_buffer = deque(maxlen=100)
+
+
+def explained_variance64(values, returns):
+    """SB3's ``explained_variance(y_pred, y_true)`` = 1 - var(y_true - y_pred) / var(y_true) in fp64 (NaN when var(y_true) is 0)."""
+    y, v = np.asarray(returns, np.float64).reshape(-1), np.asarray(values, np.float64).reshape(-1)
+    vy = float(np.var(y))
+    return float("nan") if vy == 0.0 else 1.0 - float(np.var(y - v)) / vy
+
+
+class RolloutFinish:
+    """What follows the T env steps of a rollout: GAE, SB3's Monitor for the vec-env (per-env episode return / length that
+    persist across rollouts, the last 100 finished episodes) and the rollout statistics.  On the GPU this is ONE call of
+    ``dm_rollout_finish`` (csrc/dm_ppo.hip) on the current stream, capturable into a hipGraph, with all state on the device and
+    ``read()`` as the one small device-to-host copy; on the CPU ``compute_gae`` plus the same monitor in numpy.  Episodes are
+    numbered in (rollout, step, env) order, as SB3's ``_update_info_buffer`` meets them; returns are fp32 sums in step order."""
+
+    def __init__(self, T, N, device, gamma, gae_lambda):
+        self.T, self.N, self.device, self.gamma, self.gae_lambda = int(T), int(N), torch.device(device), float(gamma), float(gae_lambda)
+        self.on_gpu = self.device.type == "cuda"
+        if self.on_gpu:
+            from . import _lib
+            self._L = _lib.load_library()
+            # one arena = one host read: [0:16) the 8 fp64 statistics, [16:216) ep_hist [2, 100], [216] ep_count (uint32)
+            self.arena = torch.zeros(16 + 2 * EP_HIST + 8, device=self.device)
+            self.stats64 = self.arena[:16].view(torch.float64)
+            self.ep_hist = self.arena[16:16 + 2 * EP_HIST]
+            self.ep_count = self.arena[16 + 2 * EP_HIST:16 + 2 * EP_HIST + 1].view(torch.int32)
+            self.ep_acc = torch.zeros(2 * self.N, device=self.device)
+            self.work_bytes = int(self._L.dm_rollout_finish_workspace_bytes(self.T, self.N))
+            self.work = torch.zeros(self.work_bytes, dtype=torch.uint8, device=self.device)
+        else:
+            self._acc = np.zeros((2, self.N), np.float32)
+            self._hist = np.zeros((2, EP_HIST), np.float32)
+            self._count = 0
+            self._stats = np.zeros(8)
+
+    def reset(self):
+        """Forget every episode, finished or running (a loaded checkpoint carries no monitor state, as in SB3)."""
+        if self.on_gpu:
+            self.arena.zero_()
+            self.ep_acc.zero_()
+        else:
+            self._acc[:] = 0
+            self._hist[:] = 0
+            self._count = 0
+            self._stats[:] = 0
+
+    def __call__(self, rew, done, val, last_val, adv=None, ret=None):
+        """rew / val [T, N] fp32, done [T, N] uint8 or fp32, last_val [N] -> (adv, ret); advances the monitor by this rollout."""
+        T, N = self.T, self.N
+        assert tuple(rew.shape) == (T, N) and tuple(done.shape) == (T, N) and tuple(val.shape) == (T, N) and last_val.numel() == N
+        if not self.on_gpu:
+            adv_, ret_ = compute_gae(rew, val, done if done.dtype == torch.float32 else done.float(), last_val, self.gamma, self.gae_lambda)
+            self._monitor_numpy(rew.numpy(), done.numpy() != 0, val.numpy(), ret_.numpy())
+            if adv is not None:
+                adv.copy_(adv_); ret.copy_(ret_)
+                return adv, ret
+            return adv_, ret_
+        import ctypes as C
+        if adv is None:
+            adv, ret = torch.empty_like(rew), torch.empty_like(rew)
+        last_val = last_val.reshape(-1)
+        for t in (rew, val, last_val, adv, ret):
+            if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+                raise ValueError("dm_rollout_finish takes contiguous fp32 device tensors")
+        if not (done.is_cuda and done.is_contiguous() and done.dtype in (torch.uint8, torch.float32)):
+            raise ValueError("dm_rollout_finish takes done flags as a contiguous uint8 or fp32 device tensor")
+        p = lambda t: C.c_void_p(t.data_ptr())
+        rc = self._L.dm_rollout_finish(T, N, p(rew), p(done), 1 if done.dtype == torch.uint8 else 0, p(val), p(last_val), self.gamma,
+                                       self.gae_lambda, p(adv), p(ret), p(self.ep_acc), p(self.ep_hist), p(self.ep_count),
+                                       p(self.stats64), p(self.work), self.work_bytes,
+                                       C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
+        if rc != 0:
+            raise RuntimeError("dm_rollout_finish failed (%d)" % rc)
+        return adv, ret
+
+    def _monitor_numpy(self, rew, fin, val, ret):
+        acc, one = self._acc, np.float32(1.0)
+        for t in range(self.T):
+            acc[0] += rew[t]
+            acc[1] += one
+            for e in np.nonzero(fin[t])[0]:                      # env order within the step
+                k = self._count % EP_HIST
+                self._hist[0, k], self._hist[1, k] = acc[0, e], acc[1, e]
+                self._count += 1
+            acc[:, fin[t]] = 0
+        y, d = ret.astype(np.float64), ret.astype(np.float64) - val.astype(np.float64)
+        vy, vd = float(np.var(y)), float(np.var(d))
+        self._stats[:] = (float(rew.astype(np.float64).sum()), float(fin.sum()), float("nan") if vy == 0.0 else 1.0 - vd / vy, vy, vd,
+                          float(rew.size), float(self._count), float(y.mean()))
+
+    def read(self):
+        """Statistics of the last rollout and the episode history, oldest episode first: one device-to-host copy on the GPU."""
+        if self.on_gpu:
+            host = self.arena.cpu()
+            st = host[:16].view(torch.float64).numpy()
+            hist = host[16:16 + 2 * EP_HIST].numpy().reshape(2, EP_HIST)
+            count = int(host[16 + 2 * EP_HIST:16 + 2 * EP_HIST + 1].view(torch.int32)[0]) & 0xFFFFFFFF
+        else:
+            st, hist, count = self._stats, self._hist, self._count
+        k = min(count, EP_HIST)
+        order = (np.arange(EP_HIST) + count) % EP_HIST if count >= EP_HIST else np.arange(k)       # slot of episode count - 100 first
+        ep_rew, ep_len = hist[0, order].copy(), hist[1, order].copy()
+        n = float(st[5]) if st[5] > 0 else 1.0
+        return dict(reward_sum=float(st[0]), dones=int(st[1]), n=int(st[5]), mean_reward=float(st[0]) / n, done_rate=float(st[1]) / n,
+                    explained_variance=float(st[2]), episodes=count, ep_returns=ep_rew, ep_lengths=ep_len,
+                    ep_rew_mean=float(np.mean(ep_rew.astype(np.float64))) if k else float("nan"),
+                    ep_len_mean=float(np.mean(ep_len.astype(np.float64))) if k else float("nan"))
+
+
 class FlatGradAllReduce:
     """One collective per optimizer step: flatten every gradient into a single fp32 buffer,
     all-reduce (sum) it over the process group (RCCL over xGMI on GPUs, gloo in CPU tests), divide by
@@ -717,8 +828,29 @@ class PPO:
         self.num_timesteps = 0
         self._last_obs = None
         self.stats = {}
+        self._finish = None      # RolloutFinish (GAE + episode monitor + rollout statistics), made with the first rollout
 
     # ------------------------------------------------------------------ rollout
+    def _rollout_finish(self):
+        """The rollout's tail, shared by every rollout path (the captured ones bake its device buffers into their graph)."""
+        if self._finish is None:
+            self._finish = RolloutFinish(self.n_steps, self.n_envs, self.device, self.gamma, self.gae_lambda)
+        return self._finish
+
+    def _rollout_stats(self):
+        """After the rollout (never inside it): one small read of what the finish left -> ``stats``."""
+        r = self._finish.read()
+        self.stats.update(mean_reward=r["mean_reward"], done_rate=r["done_rate"], ep_rew_mean=r["ep_rew_mean"], ep_len_mean=r["ep_len_mean"],
+                          episodes=r["episodes"], explained_variance=r["explained_variance"])
+        return r
+
+    def ep_history(self):
+        """(returns, lengths) of the last <= 100 finished episodes, oldest first (SB3's ``ep_info_buffer``)."""
+        if self._finish is None:
+            return np.zeros(0, np.float32), np.zeros(0, np.float32)
+        r = self._finish.read()
+        return r["ep_returns"], r["ep_lengths"]
+
     # ---- rollout-side fused kernels (csrc/dm_ppo.hip): policy head -> sampled / clamped action + logp, and the
     # per-step stores into the rollout buffer, two launches instead of ~20 small PyTorch kernels per env step
     def _fused_rollout_ok(self):
@@ -791,12 +923,13 @@ class PPO:
         if st is None:
             z = lambda *shape, dt=torch.float32: torch.zeros(*shape, device=dev, dtype=dt)
             rb = dict(obs=z(T, N, self.obs_dim), act=z(T, N, self.act_dim), rew=z(T, N), done_u8=z(T, N, dt=torch.uint8), val=z(T, N),
-                      logp=z(T, N))
+                      logp=z(T, N), adv=z(T, N), ret=z(T, N), done=z(T, N))
             last = (env.reset_tensor() if self._last_obs is None else self._last_obs).clone()
             self._rollout_scratch((N, 0))
             st = self._fp = dict(rb=rb, last=last, fwd=FusedPolicyForward(self.policy, dev), act_env=z(N, self.act_dim),
                                  streams=concurrent_streams(dev, K) if K > 1 else None, graph=None)
         rb, last, fwd = st["rb"], st["last"], st["fwd"]
+        finish = self._rollout_finish()
         if self._last_obs is not None and self._last_obs.data_ptr() != last.data_ptr():
             last.copy_(self._last_obs)
 
@@ -822,9 +955,9 @@ class PPO:
                 for s_ in st["streams"]:
                     cur.wait_stream(s_)
             self._rctr += T
-            rb["done"] = rb["done_u8"].float()
             last_val = self.policy.predict_values(last)
-            rb["adv"], rb["ret"] = compute_gae(rb["rew"], rb["val"], rb["done"], last_val, self.gamma, self.gae_lambda)
+            finish(rb["rew"], rb["done_u8"], rb["val"], last_val, rb["adv"], rb["ret"])     # once over [T, N], after the streams joined
+            rb["done"].copy_(rb["done_u8"])     # the returned buffer's flags are fp32, as on the other paths; nothing here waits for it
 
         with torch.no_grad():
             if self.rollout_graph and K > 1:
@@ -846,8 +979,7 @@ class PPO:
                 whole()
         self._last_obs = last
         self.num_timesteps += T * N
-        self.stats["mean_reward"] = float(rb["rew"].mean())
-        self.stats["done_rate"] = float(rb["done"].mean())
+        self._rollout_stats()
         return {k: v for k, v in rb.items() if k != "done_u8"}
 
     def _rollout_graph_build(self):
@@ -857,9 +989,11 @@ class PPO:
         env, T, N, dev, bd = self.env, self.n_steps, self.n_envs, self.device, self.buffer_dtype
         K = env.sub_batches
         z = lambda *shape, dt=torch.float32: torch.zeros(*shape, device=dev, dtype=dt)
-        rb = dict(obs=z(T, N, self.obs_dim, dt=bd), act=z(T, N, self.act_dim, dt=bd), rew=z(T, N), done=z(T, N), val=z(T, N), logp=z(T, N))
+        rb = dict(obs=z(T, N, self.obs_dim, dt=bd), act=z(T, N, self.act_dim, dt=bd), rew=z(T, N), done=z(T, N), val=z(T, N), logp=z(T, N),
+                  adv=z(T, N), ret=z(T, N))
         last = env.reset_tensor().clone() if self._last_obs is None else self._last_obs.clone()
         streams = concurrent_streams(dev, K)
+        finish = self._rollout_finish()
 
         def chain(k, steps):
             sl = env.sub_slices[k]
@@ -900,8 +1034,7 @@ class PPO:
                 for k in range(K):
                     cap.wait_stream(streams[k])
                 last_val = self.policy.predict_values(last)
-                adv, ret = compute_gae(rb["rew"], rb["val"], rb["done"], last_val, self.gamma, self.gae_lambda)
-        rb["adv"], rb["ret"] = adv, ret
+                finish(rb["rew"], rb["done"], rb["val"], last_val, rb["adv"], rb["ret"])      # one graph node chain, not ~6 T
         self._rollout = (g, rb, last)
 
     def _rollout_pipelined_eager(self):
@@ -929,11 +1062,10 @@ class PPO:
             for st in streams:
                 cur.wait_stream(st)
             last_val = self.policy.predict_values(last)
-            rb["adv"], rb["ret"] = compute_gae(rb["rew"], rb["val"], rb["done"], last_val, self.gamma, self.gae_lambda)
+            rb["adv"], rb["ret"] = self._rollout_finish()(rb["rew"], rb["done"], rb["val"], last_val, rb.get("adv"), rb.get("ret"))
         self._last_obs = last
         self.num_timesteps += T * N
-        self.stats["mean_reward"] = float(rb["rew"].mean())
-        self.stats["done_rate"] = float(rb["done"].mean())
+        self._rollout_stats()
         return rb
 
     def collect_rollouts(self):
@@ -950,8 +1082,7 @@ class PPO:
             g.replay()
             self._last_obs = last
             self.num_timesteps += self.n_steps * self.n_envs
-            self.stats["mean_reward"] = float(rb["rew"].mean())
-            self.stats["done_rate"] = float(rb["done"].mean())
+            self._rollout_stats()
             return rb
         T, N, dev = self.n_steps, self.n_envs, self.device
         bd = self.buffer_dtype
@@ -981,11 +1112,14 @@ class PPO:
                 buf["done"][t] = out["done"].float()
                 self._last_obs = out["obs"].clone()
             last_val = self.policy.predict_values(self._last_obs)
-            adv, ret = compute_gae(buf["rew"], buf["val"], buf["done"], last_val, self.gamma, self.gae_lambda)
+            # GPU: dm_rollout_finish (bit for bit compute_gae); CPU: compute_gae itself and the same monitor in numpy
+            adv, ret = self._rollout_finish()(buf["rew"], buf["done"], buf["val"], last_val)
         buf["adv"], buf["ret"] = adv, ret
         self.num_timesteps += T * N
-        self.stats["mean_reward"] = float(buf["rew"].mean())
-        self.stats["done_rate"] = float(buf["done"].mean())
+        self._rollout_stats()
+        if dev.type != "cuda":                                   # the torch path keeps its fp32 means
+            self.stats["mean_reward"] = float(buf["rew"].mean())
+            self.stats["done_rate"] = float(buf["done"].mean())
         return buf
 
     # ------------------------------------------------------------------ update
@@ -1289,6 +1423,9 @@ class PPO:
         return self._gloss
 
     def learn(self, total_timesteps, log_interval=1, callback=None):
+        """SB3's ``learn``: rollout, update, one log line per ``log_interval`` iterations with SB3's ``rollout/ep_rew_mean`` and
+        ``rollout/ep_len_mean`` (last 100 finished episodes; NaN until one has finished) and ``train/explained_variance``.  Under
+        ``torch.distributed`` every rank keeps the episode history of its own envs and rank 0 prints its own: nothing is reduced."""
         it = 0
         world = dist.get_world_size() if dist.is_initialized() else 1
         while self.num_timesteps * world < total_timesteps:
@@ -1302,9 +1439,10 @@ class PPO:
             if callback is not None:
                 callback(self)
             if self.rank == 0 and log_interval and it % log_interval == 0:
-                print("iter %d  steps %d  rew/step %.4f  done %.4f  loss %.4f  rollout %.2fs  train %.2fs" % (
-                    it, self.num_timesteps * world, self.stats["mean_reward"], self.stats["done_rate"],
-                    self.stats["loss"], t1 - t0, t2 - t1), flush=True)
+                print("iter %d  steps %d  rew/step %.4f  done %.4f  ep_rew_mean %.3f  ep_len_mean %.1f  explained_variance %.3f  loss %.4f  "
+                      "rollout %.2fs  train %.2fs" % (
+                          it, self.num_timesteps * world, self.stats["mean_reward"], self.stats["done_rate"], self.stats["ep_rew_mean"],
+                          self.stats["ep_len_mean"], self.stats["explained_variance"], self.stats["loss"], t1 - t0, t2 - t1), flush=True)
         return self
 
     def predict(self, obs, deterministic=True):
@@ -1324,4 +1462,6 @@ class PPO:
         if getattr(self.optimizer, "flat_pb", None) is not None:
             self.optimizer.flat_pb.copy_(self.optimizer.flat_p)
         self.num_timesteps = ck["num_timesteps"]
+        if self._finish is not None:
+            self._finish.reset()        # monitor state is not part of a checkpoint (nor is it in SB3): start it empty
         return self

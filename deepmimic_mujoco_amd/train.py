@@ -99,7 +99,7 @@ def main(argv=None):
         dash = EvalDashboardCallback(eval_env, args.motion + "_" + args.run_name, every_n_global_steps=args.eval_every, out_root=args.eval_dir)
 
     def _cb(p):
-        hist.append(dict(p.stats))
+        hist.append(dict(p.stats, timesteps=p.num_timesteps * world))
         if dash is not None:
             dash(p)
         return True
@@ -120,7 +120,10 @@ def main(argv=None):
                               "iterations": len(hist), "rollout_env_steps_per_s": per_it / roll,
                               "train_s_per_iter": trn, "overall_env_steps_per_s": per_it / (roll + trn),
                               "mean_reward_last": hist[-1]["mean_reward"], "wall_s": dt,
-                              "grad_allreduce_calls": ppo.grad_sync.calls}))
+                              "grad_allreduce_calls": ppo.grad_sync.calls,
+                              "ep_rew_mean": hist[-1]["ep_rew_mean"], "ep_len_mean": hist[-1]["ep_len_mean"],
+                              "explained_variance": hist[-1]["explained_variance"], "episodes": hist[-1]["episodes"],
+                              "curve": [(h["timesteps"], h["ep_rew_mean"], h["ep_len_mean"]) for h in hist[::max(1, len(hist) // 200)]]}))
     env.close()
     if world > 1:
         dist.destroy_process_group()

@@ -260,6 +260,25 @@ int dm_rollout_store(int N, int D, int A, const float *last_obs, const float *ac
                      const float *rew, const unsigned char *done, const float *new_obs, float *b_obs, float *b_act, float *b_val,
                      float *b_logp, float *b_rew, float *b_done, float *last_obs_out, unsigned *counter, void *stream);
 
+/* What follows the T env steps of a rollout, as one call on `stream` (capturable; csrc/dm_ppo.hip): rew / done / val are the
+ * [T, N] rollout arrays (done: unsigned char when done_is_u8, float otherwise; done[t] is the flag step t returned), last_val [N].
+ * - GAE of SB3's RolloutBuffer.compute_returns_and_advantage [EXT] into adv / ret [T, N]: per env, from t = T - 1 down,
+ *     nt = 1 - done; delta = (rew + (g * next_v) * nt) - val; last = delta + (gl * nt) * last; adv = last; ret = adv + val
+ *   with g = (float)gamma, gl = (float)(gamma * gae_lambda), every operation rounded to fp32 on its own (no contraction): bit for
+ *   bit what the elementwise PyTorch chain of ppo.compute_gae gives.
+ * - SB3's Monitor for the vec-env: ep_acc [2, N] = running return | length of every env's current episode (persistent: episodes
+ *   that span rollouts are counted whole; fp32 sums in step order), ep_hist [2, 100] = return | length of the last 100 finished
+ *   episodes, ep_count[0] = episodes finished so far.  Episodes are numbered in (call, step, env) order and episode m lives in slot
+ *   m mod 100; no atomics decide a slot, so the result is reproducible bit for bit.  Zero all three before the first call.
+ * - stats (8 doubles, fp64 accumulation in fixed order): [0] sum of rewards, [1] finished episodes of this rollout, [2] SB3's
+ *   explained_variance = 1 - var(ret - val) / var(ret) (population variances; NaN when var(ret) is 0), [3] var(ret),
+ *   [4] var(ret - val), [5] T * N, [6] ep_count after the call, [7] mean(ret).
+ * work: dm_rollout_finish_workspace_bytes(T, N) bytes of device memory, 16-byte aligned, contents irrelevant on entry. */
+long long dm_rollout_finish_workspace_bytes(int T, int N);
+int dm_rollout_finish(int T, int N, const float *rew, const void *done, int done_is_u8, const float *val, const float *last_val,
+                      double gamma, double gae_lambda, float *adv, float *ret, float *ep_acc, float *ep_hist, unsigned *ep_count,
+                      double *stats, void *work, long long work_bytes, void *stream);
+
 /* The policy side of a rollout step as ONE launch (csrc/dm_policy.hip): both trunks of SB3's actor-critic MLP
  * (obs -> H1 -> H2 -> A / 1, tanh; what [EXT] ActorCriticPolicy.forward computes for src/sb3_ppo.py:307-313), the
  * sampling head of dm_policy_sample (same draws: seed, env, counter[0] + draw_offset, action index) and the
