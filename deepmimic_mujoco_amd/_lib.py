@@ -31,7 +31,8 @@ EXPORTS = ["dm_default_config", "dm_create", "dm_destroy", "dm_last_error", "dm_
            "dm_ppo_wide_grad", "dm_ppo_wide_packed_elems", "dm_ppo_wide_dp", "dm_ppo_wide_supported",
            "dm_sac_act", "dm_sac_store", "dm_sac_gather", "dm_sac_head_fwd", "dm_sac_critic_loss", "dm_sac_actor_loss",
            "dm_sac_head_bwd", "dm_sac_linear_relu", "dm_sac_relu_bwd_colsum", "dm_sac_polyak",
-           "dm_rollout_finish", "dm_rollout_finish_workspace_bytes"]
+           "dm_rollout_finish", "dm_rollout_finish_workspace_bytes",
+           "dm_policy_forward_bf16", "dm_rollout_store_bf16", "dm_ppo_gather_bf16", "dm_flat_adam_step_gather_bf16"]
 
 
 class DmConfig(C.Structure):
@@ -65,6 +66,10 @@ class DmGatherSpec(C.Structure):
     _fields_ = [("idx", C.c_void_p), ("B", C.c_int32), ("D", C.c_int32), ("A", C.c_int32), ("reserved", C.c_int32),
                 ("obs", C.c_void_p), ("act", C.c_void_p), ("adv", C.c_void_p), ("ret", C.c_void_p), ("logp", C.c_void_p),
                 ("o_obs", C.c_void_p), ("o_act", C.c_void_p), ("o_adv", C.c_void_p), ("o_ret", C.c_void_p), ("o_logp", C.c_void_p)]
+
+
+class DmGatherSpecBf16(DmGatherSpec):
+    """include/deepmimic_hip.h: DmGatherSpecBf16 — DmGatherSpec's layout; obs / act point at bf16 rows"""
 
 
 class DmPpoWideStep(C.Structure):
@@ -120,6 +125,7 @@ def load_library():
     L.dm_linear_wgrad.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp]
     L.dm_policy_sample.argtypes = [vp, vp, i32, i32, C.c_uint64, vp, vp, vp, vp, vp, vp, vp]
     L.dm_rollout_store.argtypes = [i32, i32, i32] + [vp] * 16
+    L.dm_rollout_store_bf16.argtypes = L.dm_rollout_store.argtypes
     L.dm_policy_packed_floats.argtypes = [i32] * 4
     L.dm_ppo_mlp_workspace_floats.argtypes = [i32] * 5
     L.dm_ppo_mlp_grad.argtypes = [C.POINTER(DmPpoMlpStep), vp]
@@ -129,6 +135,7 @@ def load_library():
     L.dm_ppo_wide_supported.argtypes = [i32] * 5
     L.dm_policy_pack.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, vp]
     L.dm_policy_forward.argtypes = [vp] + [i32] * 5 + [vp] * 9 + [C.c_uint64, vp, C.c_uint32, i32] + [vp] * 9
+    L.dm_policy_forward_bf16.argtypes = L.dm_policy_forward.argtypes
     L.dm_flat_adam_step.argtypes = [vp, vp, vp, vp, i32] + [C.c_float] * 6 + [vp, i32, vp]
     L.dm_colsum.argtypes = [vp, i32, i32, vp, vp]
     L.dm_linear_tanh.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp]
@@ -137,7 +144,9 @@ def load_library():
     L.dm_flat_adam_update.argtypes = [vp, vp, vp, vp, i32] + [C.c_float] * 6 + [vp, i32, vp]
     L.dm_flat_adam_step_gather.argtypes = [vp, vp, vp, vp, i32] + [C.c_float] * 6 + [vp, i32, i32, vp, vp]
     L.dm_flat_adam_step_gather.restype = i32
+    L.dm_flat_adam_step_gather_bf16.argtypes = L.dm_flat_adam_step_gather.argtypes
     L.dm_ppo_gather.argtypes = [vp, i32, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.dm_ppo_gather_bf16.argtypes = L.dm_ppo_gather.argtypes
     L.dm_get_counters.argtypes = [vp, vp, vp, vp, vp]
     L.dm_set_counters.argtypes = [vp, vp, vp, vp]
     L.dm_set_debug.argtypes = [vp, vp]

@@ -19,6 +19,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "dm_bf16.h"
+
 namespace {
 
 constexpr int POL_R = 32;          // batch rows per workgroup
@@ -38,7 +40,8 @@ struct PolArgs {
   const unsigned *counter;
   unsigned draw_offset;
   int deterministic;
-  float *mean_out, *act, *act_env, *logp, *val, *obs_copy;
+  float *mean_out, *act_env, *logp, *val;
+  void *act, *obs_copy;            // rollout-buffer rows of the kernel's storage type: float, or bf16 as unsigned short
 };
 
 __device__ __forceinline__ unsigned pol_hash32(unsigned long long seed, unsigned a, unsigned b, unsigned c) {
@@ -133,7 +136,12 @@ __device__ __forceinline__ void pol_store_tanh(const pol_f16v &acc, const float 
   }
 }
 
+// ST = storage type of the two rollout-buffer arrays that PPO(buffer_dtype=...) narrows (act, obs_copy): float, or unsigned short for
+// bf16.  Everything the kernel computes is the same in both instantiations; the narrowing happens at those two stores alone, so
+// act_env / logp / val / mean_out do not depend on ST.
+template <typename ST>
 __global__ void __launch_bounds__(POL_THREADS) pol_forward_kernel(PolArgs a) {
+  constexpr bool BF = sizeof(ST) == 2;
   extern __shared__ __align__(16) float pol_lds[];
   const int trunk = blockIdx.y, b0 = blockIdx.x * POL_R;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -218,9 +226,17 @@ __global__ void __launch_bounds__(POL_THREADS) pol_forward_kernel(PolArgs a) {
     // the observation copy for the rollout buffer, at the very end of the (lighter) value workgroup: a global store followed by
     // loads makes the compiler wait for the write acknowledgement (possible alias), which at the top of the kernel would
     // sit in front of the first weight loads
-    if (a.obs_copy)
-      for (int i = tid; i < POL_R * a.D; i += POL_THREADS)
-        if ((b0 + i / a.D) < a.N) a.obs_copy[(size_t)b0 * a.D + i] = a.obs[(size_t)b0 * a.D + i];
+    if (a.obs_copy) {
+      if constexpr (BF) {
+        // the workgroup's rows are one contiguous range of the [N, D] array: packed pairs, scalar head / tail (dm_bf16.h)
+        const int rows = (a.N - b0) < POL_R ? (a.N - b0) : POL_R;
+        bf16_store_range(static_cast<unsigned short *>(a.obs_copy) + (size_t)b0 * a.D, a.obs + (size_t)b0 * a.D, rows * a.D, tid, POL_THREADS);
+      } else {
+        float *oc = static_cast<float *>(a.obs_copy);
+        for (int i = tid; i < POL_R * a.D; i += POL_THREADS)
+          if ((b0 + i / a.D) < a.N) oc[(size_t)b0 * a.D + i] = a.obs[(size_t)b0 * a.D + i];
+      }
+    }
     return;
   }
   // eight threads per row, two action pairs each (A <= 32): same draws as ppo_sample_kernel (seed, env, counter, index)
@@ -249,7 +265,8 @@ __global__ void __launch_bounds__(POL_THREADS) pol_forward_kernel(PolArgs a) {
         const float v = m + expf(ls) * eps[t];
         if (ok) {
           if (a.mean_out) a.mean_out[(size_t)e * a.A + c] = m;
-          a.act[(size_t)e * a.A + c] = v;
+          if constexpr (BF) static_cast<unsigned short *>(a.act)[(size_t)e * a.A + c] = (unsigned short)bf16_rne(v);
+          else static_cast<float *>(a.act)[(size_t)e * a.A + c] = v;
           a.act_env[(size_t)e * a.A + c] = fminf(fmaxf(v, a.lo[c]), a.hi[c]);
         }
         lp += -0.5f * eps[t] * eps[t] - ls - 0.9189385332046727f;
@@ -307,24 +324,25 @@ extern "C" int dm_policy_pack(const float *W1, const float *W2, const float *W3,
   return hipGetLastError() == hipSuccess ? 0 : -5;
 }
 
-extern "C" int dm_policy_forward(const float *obs, int N, int D, int H1, int H2, int A, const float *pi_packed, const float *pi_b1,
-                                 const float *pi_b2, const float *pi_b3, const float *vf_packed, const float *vf_b1,
-                                 const float *vf_b2, const float *vf_b3, const float *log_std, unsigned long long seed,
-                                 const unsigned *counter, unsigned draw_offset, int deterministic, const float *lo, const float *hi,
-                                 float *mean_out, float *act, float *act_env, float *logp, float *val, float *obs_copy, void *stream) {
+template <typename ST>
+static int pol_forward_launch(const float *obs, int N, int D, int H1, int H2, int A, const float *pi_packed, const float *pi_b1,
+                              const float *pi_b2, const float *pi_b3, const float *vf_packed, const float *vf_b1, const float *vf_b2,
+                              const float *vf_b3, const float *log_std, unsigned long long seed, const unsigned *counter,
+                              unsigned draw_offset, int deterministic, const float *lo, const float *hi, float *mean_out, ST *act,
+                              float *act_env, float *logp, float *val, ST *obs_copy, void *stream) {
   if (!obs || N < 1 || !pol_dims_ok(D, H1, H2, A) || !pi_packed || !pi_b1 || !pi_b2 || !pi_b3 || !vf_packed || !vf_b1 || !vf_b2 ||
       !vf_b3 || !log_std || !counter || !lo || !hi || !act || !act_env || !logp || !val)
     return -22;
   if ((reinterpret_cast<uintptr_t>(pi_packed) | reinterpret_cast<uintptr_t>(vf_packed)) & 15) return -22;
   const size_t lds = pol_lds_bytes(D, H1);
   if (lds > 160 * 1024) return -22;
-  // hipFuncSetAttribute applies to the CURRENT device: remember the raised limit per device ordinal
+  // hipFuncSetAttribute applies to the CURRENT device (and to this instantiation): remember the raised limit per device ordinal
   static size_t lds_allowed[64];
   int dev_id = 0;
   if (hipGetDevice(&dev_id) != hipSuccess || dev_id < 0 || dev_id >= 64) return -5;
   const size_t allowed = lds_allowed[dev_id] ? lds_allowed[dev_id] : (size_t)64 * 1024;
   if (lds > allowed) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(pol_forward_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
+    if (hipFuncSetAttribute(reinterpret_cast<const void *>(pol_forward_kernel<ST>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
         hipSuccess)
       return -5;
     lds_allowed[dev_id] = lds;
@@ -336,6 +354,27 @@ extern "C" int dm_policy_forward(const float *obs, int N, int D, int H1, int H2,
   a.log_std = log_std; a.lo = lo; a.hi = hi; a.seed = seed; a.counter = counter; a.draw_offset = draw_offset;
   a.deterministic = deterministic;
   a.mean_out = mean_out; a.act = act; a.act_env = act_env; a.logp = logp; a.val = val; a.obs_copy = obs_copy;
-  hipLaunchKernelGGL(pol_forward_kernel, dim3((N + POL_R - 1) / POL_R, 2), dim3(POL_THREADS), lds, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(pol_forward_kernel<ST>, dim3((N + POL_R - 1) / POL_R, 2), dim3(POL_THREADS), lds, (hipStream_t)stream, a);
   return hipGetLastError() == hipSuccess ? 0 : -5;
+}
+
+extern "C" int dm_policy_forward(const float *obs, int N, int D, int H1, int H2, int A, const float *pi_packed, const float *pi_b1,
+                                 const float *pi_b2, const float *pi_b3, const float *vf_packed, const float *vf_b1,
+                                 const float *vf_b2, const float *vf_b3, const float *log_std, unsigned long long seed,
+                                 const unsigned *counter, unsigned draw_offset, int deterministic, const float *lo, const float *hi,
+                                 float *mean_out, float *act, float *act_env, float *logp, float *val, float *obs_copy, void *stream) {
+  return pol_forward_launch<float>(obs, N, D, H1, H2, A, pi_packed, pi_b1, pi_b2, pi_b3, vf_packed, vf_b1, vf_b2, vf_b3, log_std, seed,
+                                   counter, draw_offset, deterministic, lo, hi, mean_out, act, act_env, logp, val, obs_copy, stream);
+}
+
+// the same launch with act / obs_copy stored as bf16 (round to nearest even at the store; every other output bit for bit as above)
+extern "C" int dm_policy_forward_bf16(const float *obs, int N, int D, int H1, int H2, int A, const float *pi_packed, const float *pi_b1,
+                                      const float *pi_b2, const float *pi_b3, const float *vf_packed, const float *vf_b1,
+                                      const float *vf_b2, const float *vf_b3, const float *log_std, unsigned long long seed,
+                                      const unsigned *counter, unsigned draw_offset, int deterministic, const float *lo, const float *hi,
+                                      float *mean_out, unsigned short *act, float *act_env, float *logp, float *val,
+                                      unsigned short *obs_copy, void *stream) {
+  return pol_forward_launch<unsigned short>(obs, N, D, H1, H2, A, pi_packed, pi_b1, pi_b2, pi_b3, vf_packed, vf_b1, vf_b2, vf_b3, log_std,
+                                            seed, counter, draw_offset, deterministic, lo, hi, mean_out, act, act_env, logp, val, obs_copy,
+                                            stream);
 }

@@ -14,6 +14,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "dm_bf16.h"
+
 namespace {
 
 constexpr int PPO_MAXA = 32;     // action dimensions supported (28 here)
@@ -605,7 +607,45 @@ __global__ void ppo_gather_kernel(const long long *idx, int B, const float *obs,
   for (int c = threadIdx.x; c < A; c += blockDim.x) o_act[(size_t)r * A + c] = act[(size_t)s * A + c];
   if (threadIdx.x == 0) { o_adv[r] = adv[s]; o_ret[r] = ret[s]; o_logp[r] = logp[s]; }
 }
+
+// One gathered row of a bf16 rollout buffer (PPO(buffer_dtype=torch.bfloat16)) widened into the fp32 static minibatch, by 128
+// threads (t): obs / act rows through the staged wide loads of dm_bf16.h (16-byte loads from the row's first 16-byte boundary on,
+// 2-byte loads for the <= 7 elements on either side, coalesced fp32 stores after one barrier); the widening is `<< 16`: exact.
+// live = false: the threads only keep the barrier company (odd B in the two-rows-per-block form).
+__device__ __forceinline__ void ppo_gather_row_bf16(bool live, long long s, int r, int t, const unsigned short *obs, int D,
+                                                    const unsigned short *act, int A, const float *adv, const float *ret,
+                                                    const float *logp, float *o_obs, float *o_act, float *o_adv, float *o_ret,
+                                                    float *o_logp, unsigned short *stage) {
+  int oo = 0, oa = 0;
+  if (live) {
+    oo = bf16_row_to_lds(obs + (size_t)s * D, D, t, stage);
+    oa = bf16_row_to_lds(act + (size_t)s * A, A, t, stage + BF16_STAGE);
+  }
+  __syncthreads();
+  if (!live) return;
+  for (int c = t; c < D; c += 128) o_obs[(size_t)r * D + c] = bf16_widen(stage[oo + c]);
+  for (int c = t; c < A; c += 128) o_act[(size_t)r * A + c] = bf16_widen(stage[BF16_STAGE + oa + c]);
+  if (t == 0) { o_adv[r] = adv[s]; o_ret[r] = ret[s]; o_logp[r] = logp[s]; }
+}
+__global__ void __launch_bounds__(128) ppo_gather_bf16_kernel(const long long *idx, int B, const unsigned short *obs, int D,
+                                                              const unsigned short *act, int A, const float *adv, const float *ret,
+                                                              const float *logp, float *o_obs, float *o_act, float *o_adv, float *o_ret,
+                                                              float *o_logp) {
+  __shared__ __align__(16) unsigned short stage[2 * BF16_STAGE];
+  const int r = blockIdx.x;              // one 128-thread block per gathered row (grid = B)
+  ppo_gather_row_bf16(true, idx[r], r, threadIdx.x, obs, D, act, A, adv, ret, logp, o_obs, o_act, o_adv, o_ret, o_logp, stage);
+}
 }  // namespace
+
+extern "C" int dm_ppo_gather_bf16(const long long *idx, int B, const unsigned short *obs, int D, const unsigned short *act, int A,
+                                  const float *adv, const float *ret, const float *logp, float *o_obs, float *o_act, float *o_adv,
+                                  float *o_ret, float *o_logp, void *stream) {
+  if (!idx || B < 1 || !obs || !act || !adv || !ret || !logp || !o_obs || !o_act || !o_adv || !o_ret || !o_logp) return -22;
+  if (D < 1 || A < 1 || D > BF16_ROW_MAX || A > BF16_ROW_MAX) return -22;
+  hipLaunchKernelGGL(ppo_gather_bf16_kernel, dim3(B), dim3(128), 0, (hipStream_t)stream, idx, B, obs, D, act, A, adv, ret, logp, o_obs,
+                     o_act, o_adv, o_ret, o_logp);
+  return hipGetLastError() == hipSuccess ? 0 : -5;
+}
 
 extern "C" int dm_ppo_gather(const long long *idx, int B, const float *obs, int D, const float *act, int A, const float *adv,
                              const float *ret, const float *logp, float *o_obs, float *o_act, float *o_adv, float *o_ret,
@@ -630,17 +670,29 @@ namespace {
 // inside a graph; three other ways of hiding it lost: DESIGN 6).  Two rows per block, 128 threads each.
 struct AdamGather {
   const long long *idx; int B, D, A;
-  const float *obs, *act, *adv, *ret, *logp;
+  const void *obs, *act;                 // rows of the kernel's storage type: float, or bf16 as unsigned short
+  const float *adv, *ret, *logp;
   float *o_obs, *o_act, *o_adv, *o_ret, *o_logp;
 };
+// ST = storage type of the gathered obs / act arrays (float | unsigned short = bf16); the norm blocks do not depend on it
+template <typename ST>
 __global__ void adam_sumsq_kernel(const float *g, int n, float *state, int bump_step, int nsum, AdamGather G) {
   if ((int)blockIdx.x >= nsum) {
     const int r = 2 * ((int)blockIdx.x - nsum) + (threadIdx.x >> 7), t = threadIdx.x & 127;
-    if (r >= G.B) return;
-    const long long sr = G.idx[r];
-    for (int c = t; c < G.D; c += 128) G.o_obs[(size_t)r * G.D + c] = G.obs[(size_t)sr * G.D + c];
-    for (int c = t; c < G.A; c += 128) G.o_act[(size_t)r * G.A + c] = G.act[(size_t)sr * G.A + c];
-    if (t == 0) { G.o_adv[r] = G.adv[sr]; G.o_ret[r] = G.ret[sr]; G.o_logp[r] = G.logp[sr]; }
+    if constexpr (sizeof(ST) == 2) {
+      __shared__ __align__(16) unsigned short stage[2][2 * BF16_STAGE];
+      const bool live = r < G.B;         // odd B: the second half of the last block waits at the barrier and does nothing else
+      ppo_gather_row_bf16(live, live ? G.idx[r] : 0, r, t, static_cast<const unsigned short *>(G.obs), G.D,
+                          static_cast<const unsigned short *>(G.act), G.A, G.adv, G.ret, G.logp, G.o_obs, G.o_act, G.o_adv, G.o_ret,
+                          G.o_logp, stage[threadIdx.x >> 7]);
+    } else {
+      if (r >= G.B) return;
+      const float *obs = static_cast<const float *>(G.obs), *act = static_cast<const float *>(G.act);
+      const long long sr = G.idx[r];
+      for (int c = t; c < G.D; c += 128) G.o_obs[(size_t)r * G.D + c] = obs[(size_t)sr * G.D + c];
+      for (int c = t; c < G.A; c += 128) G.o_act[(size_t)r * G.A + c] = act[(size_t)sr * G.A + c];
+      if (t == 0) { G.o_adv[r] = G.adv[sr]; G.o_ret[r] = G.ret[sr]; G.o_logp[r] = G.logp[sr]; }
+    }
     return;
   }
   if (bump_step && blockIdx.x == 0 && threadIdx.x == 0) state[1] += 1.f;    // Adam's step count (read by the update launch)
@@ -701,7 +753,7 @@ __global__ void adam_update_kernel(float *p, const float *g, float *m, float *v,
 
 static int flat_adam_launch(float *p, const float *g, float *m, float *v, int n, float lr, float beta1, float beta2, float eps,
                             float max_norm, float grad_scale, float *state2, int state2_floats, void *stream, int begin,
-                            const DmGatherSpec *next = nullptr) {
+                            const DmGatherSpec *next = nullptr, int next_bf16 = 0) {
   if (!p || !g || !m || !v || !state2 || n < 1 || !(grad_scale > 0.f)) return -22;
   if (state2_floats < 2 + DM_ADAM_PARTIALS) return -22;   // the partial sums live behind the two scalars: a shorter buffer would be overrun
   AdamGather G;
@@ -710,6 +762,7 @@ static int flat_adam_launch(float *p, const float *g, float *m, float *v, int n,
   if (next) {
     if (!next->idx || next->B < 1 || next->D < 1 || next->A < 1 || !next->obs || !next->act || !next->adv || !next->ret || !next->logp ||
         !next->o_obs || !next->o_act || !next->o_adv || !next->o_ret || !next->o_logp) return -22;
+    if (next_bf16 && (next->D > BF16_ROW_MAX || next->A > BF16_ROW_MAX)) return -22;
     G.idx = next->idx; G.B = next->B; G.D = next->D; G.A = next->A;
     G.obs = next->obs; G.act = next->act; G.adv = next->adv; G.ret = next->ret; G.logp = next->logp;
     G.o_obs = next->o_obs; G.o_act = next->o_act; G.o_adv = next->o_adv; G.o_ret = next->o_ret; G.o_logp = next->o_logp;
@@ -718,7 +771,9 @@ static int flat_adam_launch(float *p, const float *g, float *m, float *v, int n,
   hipStream_t s = (hipStream_t)stream;
   int blocks = (n + 256 * 8 - 1) / (256 * 8);
   if (blocks > DM_ADAM_PARTIALS) blocks = DM_ADAM_PARTIALS;
-  hipLaunchKernelGGL(adam_sumsq_kernel, dim3(blocks + gather_blocks), dim3(256), 0, s, g, n, state2, begin, blocks, G);   // step count folded in: two launches
+  // step count folded in: two launches
+  if (next && next_bf16) hipLaunchKernelGGL(adam_sumsq_kernel<unsigned short>, dim3(blocks + gather_blocks), dim3(256), 0, s, g, n, state2, begin, blocks, G);
+  else hipLaunchKernelGGL(adam_sumsq_kernel<float>, dim3(blocks + gather_blocks), dim3(256), 0, s, g, n, state2, begin, blocks, G);
   hipLaunchKernelGGL(adam_update_kernel, dim3(blocks), dim3(256), 0, s, p, g, m, v, n, lr, beta1, beta2, eps, max_norm, grad_scale, state2);
   return hipGetLastError() == hipSuccess ? 0 : -5;
 }
@@ -734,6 +789,18 @@ extern "C" int dm_flat_adam_step_gather(float *p, const float *g, float *m, floa
                                         float max_norm, float grad_scale, float *state2, int state2_floats, int begin,
                                         const DmGatherSpec *next, void *stream) {
   return flat_adam_launch(p, g, m, v, n, lr, beta1, beta2, eps, max_norm, grad_scale, state2, state2_floats, stream, begin ? 1 : 0, next);
+}
+// the same with the next minibatch gathered from a bf16 rollout buffer: DmGatherSpecBf16 has DmGatherSpec's layout, obs / act are bf16 rows
+extern "C" int dm_flat_adam_step_gather_bf16(float *p, const float *g, float *m, float *v, int n, float lr, float beta1, float beta2,
+                                             float eps, float max_norm, float grad_scale, float *state2, int state2_floats, int begin,
+                                             const DmGatherSpecBf16 *next, void *stream) {
+  if (!next) return -22;
+  DmGatherSpec sp;
+  sp.idx = next->idx; sp.B = next->B; sp.D = next->D; sp.A = next->A; sp.reserved = 0;
+  sp.obs = reinterpret_cast<const float *>(next->obs); sp.act = reinterpret_cast<const float *>(next->act);   // retyped in the kernel
+  sp.adv = next->adv; sp.ret = next->ret; sp.logp = next->logp;
+  sp.o_obs = next->o_obs; sp.o_act = next->o_act; sp.o_adv = next->o_adv; sp.o_ret = next->o_ret; sp.o_logp = next->o_logp;
+  return flat_adam_launch(p, g, m, v, n, lr, beta1, beta2, eps, max_norm, grad_scale, state2, state2_floats, stream, begin ? 1 : 0, &sp, 1);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -780,16 +847,28 @@ __global__ void ppo_sample_kernel(const float *mean, const float *log_std, int N
 }
 
 // rollout buffer row t <- (obs the policy saw, action, value, logp, reward, done); last_obs <- the env's new obs
+// ST = storage type of b_obs / b_act: float, or unsigned short for a bf16 rollout buffer (round to nearest even at the store)
+template <typename ST>
 __global__ void ppo_store_kernel(int N, int D, int A, const float *last_obs, const float *act, const float *val, const float *logp,
-                                 const float *rew, const unsigned char *done, const float *new_obs, float *b_obs, float *b_act,
+                                 const float *rew, const unsigned char *done, const float *new_obs, ST *b_obs, ST *b_act,
                                  float *b_val, float *b_logp, float *b_rew, float *b_done, float *last_obs_out, unsigned *counter) {
   const int e = blockIdx.x;
   if (e >= N) return;
-  for (int c = threadIdx.x; c < D; c += blockDim.x) {
-    b_obs[(size_t)e * D + c] = last_obs[(size_t)e * D + c];
-    last_obs_out[(size_t)e * D + c] = new_obs[(size_t)e * D + c];
+  if constexpr (sizeof(ST) == 2) {
+    // a row is contiguous: packed pairs with a scalar head / tail (dm_bf16.h).  last_obs_out may BE last_obs (the rollout loops
+    // pass the same rows), and the pair lanes read other elements than they overwrite: the whole row is filed before any of it
+    // is replaced
+    bf16_store_range(b_obs + (size_t)e * D, last_obs + (size_t)e * D, D, threadIdx.x, blockDim.x);
+    bf16_store_range(b_act + (size_t)e * A, act + (size_t)e * A, A, threadIdx.x, blockDim.x);
+    __syncthreads();
+    for (int c = threadIdx.x; c < D; c += blockDim.x) last_obs_out[(size_t)e * D + c] = new_obs[(size_t)e * D + c];
+  } else {
+    for (int c = threadIdx.x; c < D; c += blockDim.x) {
+      b_obs[(size_t)e * D + c] = last_obs[(size_t)e * D + c];
+      last_obs_out[(size_t)e * D + c] = new_obs[(size_t)e * D + c];
+    }
+    for (int c = threadIdx.x; c < A; c += blockDim.x) b_act[(size_t)e * A + c] = act[(size_t)e * A + c];
   }
-  for (int c = threadIdx.x; c < A; c += blockDim.x) b_act[(size_t)e * A + c] = act[(size_t)e * A + c];
   if (threadIdx.x == 0) {
     b_val[e] = val[e]; b_logp[e] = logp[e]; b_rew[e] = rew[e]; b_done[e] = done[e] ? 1.f : 0.f;
     if (e == 0 && counter) counter[0] += 1u;
@@ -814,8 +893,20 @@ extern "C" int dm_rollout_store(int N, int D, int A, const float *last_obs, cons
   if (N < 1 || !last_obs || !act || !val || !logp || !rew || !done || !new_obs || !b_obs || !b_act || !b_val || !b_logp || !b_rew ||
       !b_done || !last_obs_out)
     return -22;
-  hipLaunchKernelGGL(ppo_store_kernel, dim3(N), dim3(128), 0, (hipStream_t)stream, N, D, A, last_obs, act, val, logp, rew, done, new_obs,
-                     b_obs, b_act, b_val, b_logp, b_rew, b_done, last_obs_out, counter);
+  hipLaunchKernelGGL(ppo_store_kernel<float>, dim3(N), dim3(128), 0, (hipStream_t)stream, N, D, A, last_obs, act, val, logp, rew, done,
+                     new_obs, b_obs, b_act, b_val, b_logp, b_rew, b_done, last_obs_out, counter);
+  return hipGetLastError() == hipSuccess ? 0 : -5;
+}
+
+extern "C" int dm_rollout_store_bf16(int N, int D, int A, const float *last_obs, const float *act, const float *val, const float *logp,
+                                     const float *rew, const unsigned char *done, const float *new_obs, unsigned short *b_obs,
+                                     unsigned short *b_act, float *b_val, float *b_logp, float *b_rew, float *b_done,
+                                     float *last_obs_out, unsigned *counter, void *stream) {
+  if (N < 1 || D < 1 || A < 1 || !last_obs || !act || !val || !logp || !rew || !done || !new_obs || !b_obs || !b_act || !b_val || !b_logp ||
+      !b_rew || !b_done || !last_obs_out)
+    return -22;
+  hipLaunchKernelGGL(ppo_store_kernel<unsigned short>, dim3(N), dim3(128), 0, (hipStream_t)stream, N, D, A, last_obs, act, val, logp, rew,
+                     done, new_obs, b_obs, b_act, b_val, b_logp, b_rew, b_done, last_obs_out, counter);
   return hipGetLastError() == hipSuccess ? 0 : -5;
 }
 

@@ -285,7 +285,11 @@ class FusedPolicyForward:
         import ctypes as C
         p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
         pi, vf = self.pi, self.vf
-        rc = self.lib.dm_policy_forward(
+        # the storage type of the two rollout-buffer outputs picks the entry point (PPO(buffer_dtype=...)); all else is fp32
+        if act.dtype not in (torch.float32, torch.bfloat16) or (obs_copy is not None and obs_copy.dtype != act.dtype):
+            raise ValueError("dm_policy_forward stores act / obs_copy as fp32 or bf16, both of one type")
+        entry = self.lib.dm_policy_forward_bf16 if act.dtype == torch.bfloat16 else self.lib.dm_policy_forward
+        rc = entry(
             p(obs), obs.shape[0], self.D, self.H1, self.H2, self.A, p(self.packed[0]), p(pi[0].bias), p(pi[1].bias), p(pi[2].bias),
             p(self.packed[1]), p(vf[0].bias), p(vf[1].bias), p(vf[2].bias), p(self.policy.log_std), C.c_uint64(seed), p(counter),
             C.c_uint32(draw_offset), int(bool(deterministic)), p(lo), p(hi), p(mean_out), p(act), p(act_env), p(logp), p(val),
@@ -646,6 +650,16 @@ class FlatGradAllReduce:
             off += n
 
 
+def gather_storage(flat, idx=None):
+    """Which minibatch-gather kernel serves a flattened rollout buffer: "fp32" (dm_ppo_gather), "bf16" (dm_ppo_gather_bf16: obs and
+    act stored in bf16, PPO(buffer_dtype=torch.bfloat16)) or None (anything else: PyTorch indexing)."""
+    if idx is not None and idx.dtype != torch.int64:
+        return None
+    if any(flat[k].dtype != torch.float32 for k in ("adv", "ret", "logp")) or flat["obs"].dtype != flat["act"].dtype:
+        return None
+    return {torch.float32: "fp32", torch.bfloat16: "bf16"}.get(flat["obs"].dtype)
+
+
 class FlatAdam:
     """clip_grad_norm_ + Adam on one flat buffer (`dm_flat_adam_step`, csrc/dm_ppo.hip): every parameter of the policy
     becomes a view of `flat_p`, every gradient is gathered in `flat_g` (the HipLinear layers write theirs there
@@ -731,13 +745,15 @@ class FlatAdam:
         else:
             flat, idx, out = gather_next
             assert idx.dtype == torch.int64 and idx.is_contiguous()
+            kind = gather_storage(flat, idx)
+            assert kind is not None, "gather_next: fp32 or bf16 obs / act, fp32 adv / ret / logp, int64 idx"
             for k in ("obs", "act", "adv", "ret", "logp"):
-                assert flat[k].dtype == torch.float32 and flat[k].is_contiguous() and out[k].dtype == torch.float32 and out[k].is_contiguous()
-            gs = _lib.DmGatherSpec()
+                assert flat[k].is_contiguous() and out[k].dtype == torch.float32 and out[k].is_contiguous()
+            gs = _lib.DmGatherSpecBf16() if kind == "bf16" else _lib.DmGatherSpec()
             gs.idx, gs.B, gs.D, gs.A = idx.data_ptr(), int(idx.numel()), int(flat["obs"].shape[1]), int(flat["act"].shape[1])
             gs.obs, gs.act, gs.adv, gs.ret, gs.logp = (flat[k].data_ptr() for k in ("obs", "act", "adv", "ret", "logp"))
             gs.o_obs, gs.o_act, gs.o_adv, gs.o_ret, gs.o_logp = (out[k].data_ptr() for k in ("obs", "act", "adv", "ret", "logp"))
-            rc = L.dm_flat_adam_step_gather(*common, int(bool(begin)), C.byref(gs), stream)
+            rc = (L.dm_flat_adam_step_gather_bf16 if kind == "bf16" else L.dm_flat_adam_step_gather)(*common, int(bool(begin)), C.byref(gs), stream)
         if rc != 0:
             raise RuntimeError("dm_flat_adam_step failed (%d)" % rc)
         if self.flat_pb is not None:
@@ -854,7 +870,8 @@ class PPO:
     # ---- rollout-side fused kernels (csrc/dm_ppo.hip): policy head -> sampled / clamped action + logp, and the
     # per-step stores into the rollout buffer, two launches instead of ~20 small PyTorch kernels per env step
     def _fused_rollout_ok(self):
-        return (self.fused_rollout and self.device.type == "cuda" and self.buffer_dtype == torch.float32)
+        # fp32 or bf16 storage of the buffer's obs / act (the kernels narrow at the store); anything else: the plain loop
+        return (self.fused_rollout and self.device.type == "cuda" and self.buffer_dtype in (torch.float32, torch.bfloat16))
 
     def _rollout_scratch(self, key):
         sc = getattr(self, "_rsc", {})
@@ -896,7 +913,10 @@ class PPO:
         from . import _lib
         p = lambda x: C.c_void_p(x.data_ptr())
         n = val.shape[0]
-        rc = _lib.load_library().dm_rollout_store(
+        L = _lib.load_library()
+        if rb["obs"].dtype != rb["act"].dtype or rb["obs"].dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError("dm_rollout_store files obs / act as fp32 or bf16, both of one type")
+        rc = (L.dm_rollout_store_bf16 if rb["obs"].dtype == torch.bfloat16 else L.dm_rollout_store)(
             n, self.obs_dim, self.act_dim, p(last[sl]), p(sc["act"]), p(val), p(sc["logp"]), p(out["rew"]), p(out["done"]), p(out["obs"]),
             p(rb["obs"][t, sl]), p(rb["act"][t, sl]), p(rb["val"][t, sl]), p(rb["logp"][t, sl]), p(rb["rew"][t, sl]),
             p(rb["done"][t, sl]), p(last[sl]), p(self._ctr(env_index)) if bump else None,
@@ -922,7 +942,8 @@ class PPO:
         st = getattr(self, "_fp", None)
         if st is None:
             z = lambda *shape, dt=torch.float32: torch.zeros(*shape, device=dev, dtype=dt)
-            rb = dict(obs=z(T, N, self.obs_dim), act=z(T, N, self.act_dim), rew=z(T, N), done_u8=z(T, N, dt=torch.uint8), val=z(T, N),
+            bd = self.buffer_dtype
+            rb = dict(obs=z(T, N, self.obs_dim, dt=bd), act=z(T, N, self.act_dim, dt=bd), rew=z(T, N), done_u8=z(T, N, dt=torch.uint8), val=z(T, N),
                       logp=z(T, N), adv=z(T, N), ret=z(T, N), done=z(T, N))
             last = (env.reset_tensor() if self._last_obs is None else self._last_obs).clone()
             self._rollout_scratch((N, 0))
@@ -1043,8 +1064,9 @@ class PPO:
         env, T, N, dev = self.env, self.n_steps, self.n_envs, self.device
         K = env.sub_batches
         if getattr(self, "_pipe", None) is None:
-            z = lambda *shape: torch.zeros(*shape, device=dev)
-            rb = dict(obs=z(T, N, self.obs_dim), act=z(T, N, self.act_dim), rew=z(T, N), done=z(T, N), val=z(T, N), logp=z(T, N))
+            z = lambda *shape, dt=torch.float32: torch.zeros(*shape, device=dev, dtype=dt)
+            bd = self.buffer_dtype
+            rb = dict(obs=z(T, N, self.obs_dim, dt=bd), act=z(T, N, self.act_dim, dt=bd), rew=z(T, N), done=z(T, N), val=z(T, N), logp=z(T, N))
             last = env.reset_tensor().clone() if self._last_obs is None else self._last_obs.clone()
             self._pipe = (rb, last, concurrent_streams(dev, K))
         rb, last, streams = self._pipe
@@ -1068,14 +1090,33 @@ class PPO:
         self._rollout_stats()
         return rb
 
-    def collect_rollouts(self):
+    def _rollout_route(self):
+        """Which implementation collect_rollouts() runs: the one place that decides it."""
         if self._fused_policy_ok():
+            return "policy_forward"
+        halves = getattr(self.env, "sub_batches", 1) > 1 and hasattr(self.env, "step_sub")
+        if not self.rollout_graph and self._fused_rollout_ok() and halves:
+            return "pipelined"
+        if self.rollout_graph and self.device.type == "cuda" and halves:
+            return "graph"
+        return "loop"
+
+    def rollout_path(self):
+        """Name of the rollout path this configuration takes, for run records: "policy_forward" (dm_policy_forward + dm_step per
+        step, host-driven or captured), "sample_store" (library GEMMs + dm_policy_sample + dm_rollout_store, one stream or one per
+        sub-batch), "graph" (the captured rollout of _rollout_graph_build) or "plain" (PyTorch ops only)."""
+        route = self._rollout_route()
+        if route == "loop":
+            return "sample_store" if self._fused_rollout_ok() else "plain"
+        return "sample_store" if route == "pipelined" else route
+
+    def collect_rollouts(self):
+        route = self._rollout_route()
+        if route == "policy_forward":
             return self._rollout_fused_policy()
-        if (not self.rollout_graph and self._fused_rollout_ok() and getattr(self.env, "sub_batches", 1) > 1
-                and hasattr(self.env, "step_sub")):
+        if route == "pipelined":
             return self._rollout_pipelined_eager()
-        if (self.rollout_graph and self.device.type == "cuda" and getattr(self.env, "sub_batches", 1) > 1
-                and hasattr(self.env, "step_sub")):
+        if route == "graph":
             if getattr(self, "_rollout", None) is None:
                 self._rollout_graph_build()
             g, rb, last = self._rollout
@@ -1284,7 +1325,11 @@ class PPO:
         import ctypes as C
         from . import _lib
         p = lambda t: C.c_void_p(t.data_ptr())
-        rc = _lib.load_library().dm_ppo_gather(
+        L = _lib.load_library()
+        kind = gather_storage(flat, idx)
+        if kind is None:
+            raise ValueError("dm_ppo_gather takes fp32 or bf16 obs / act, fp32 adv / ret / logp and int64 indices")
+        rc = (L.dm_ppo_gather_bf16 if kind == "bf16" else L.dm_ppo_gather)(
             p(idx), int(idx.numel()), p(flat["obs"]), self.obs_dim, p(flat["act"]), flat["act"].shape[1], p(flat["adv"]),
             p(flat["ret"]), p(flat["logp"]), p(g["obs"]), p(g["act"]), p(g["adv"]), p(g["ret"]), p(g["logp"]),
             C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
@@ -1339,12 +1384,12 @@ class PPO:
 
     def _epoch_graph_ok(self, flat, n):
         return (self.use_hip_graph and self.device.type == "cuda" and n % self.batch_size == 0 and self.epoch_graph
-                and all(flat[k].dtype == torch.float32 for k in ("obs", "act", "adv", "ret", "logp")))
+                and gather_storage(flat) is not None)
 
     def _dist_graph_ok(self, flat, n):
         return (self.dist_graph and self.flat_adam and self.device.type == "cuda" and n % self.batch_size == 0
                 and dist.is_initialized() and dist.get_world_size() > 1
-                and all(flat[k].dtype == torch.float32 for k in ("obs", "act", "adv", "ret", "logp")))
+                and gather_storage(flat) is not None)
 
     def _dist_graphs(self, flat, n):
         """Two captured graphs per minibatch for the multi-rank learner (see train())."""
@@ -1370,6 +1415,7 @@ class PPO:
             grad()
             adam()
 
+        dg["gin"] = gin          # the static minibatch the graphs read (fp32 whatever the buffer's storage type)
         (dg["grad"], dg["adam"]), _ = self._capture_with_restore(warm, [grad, adam])
         self._dg = dg
         return dg
@@ -1401,6 +1447,7 @@ class PPO:
                 if not self._on_dev:
                     eg["loss"].add_(loss)
 
+        eg["gin"] = gin          # the static minibatch the graph reads (fp32 whatever the buffer's storage type)
         eg["graph"], _ = self._capture_with_restore(warm, body)
         self._eg = eg
         return eg
@@ -1412,9 +1459,9 @@ class PPO:
             kw = {("old_logp" if k == "logp" else k): v for k, v in self._gin.items()}
             self._graph, self._gloss = self._capture_with_restore(lambda: self._minibatch_step(**kw), lambda: self._minibatch_step(**kw))
         g = self._gin
-        if flat["obs"].dtype == torch.float32 and flat["act"].dtype == torch.float32 and idx.dtype == torch.int64:
+        if gather_storage(flat, idx) is not None and idx.is_contiguous():    # fp32 or bf16 obs / act: one launch
             self._gather_minibatch(flat, idx, g)
-        else:  # bf16 rollout buffers (config 5): gather + widen with PyTorch ops
+        else:  # what the kernels do not take (other storage types, non-int64 indices): gather + widen with PyTorch ops
             g["obs"].copy_(flat["obs"][idx]); g["act"].copy_(flat["act"][idx])
             torch.index_select(flat["adv"], 0, idx, out=g["adv"])
             torch.index_select(flat["ret"], 0, idx, out=g["ret"])

@@ -117,6 +117,7 @@ def main(argv=None):
             per_it = args.envs * args.horizon * world
             print(json.dumps({"workload": "ppo", "n_gpus": world, "envs_per_gpu": args.envs, "horizon": args.horizon,
                               "arch": args.arch, "epochs": args.epochs, "minibatch": args.minibatch,
+                              "buffer_dtype": str(ppo.buffer_dtype).replace("torch.", ""), "rollout_path": ppo.rollout_path(),
                               "iterations": len(hist), "rollout_env_steps_per_s": per_it / roll,
                               "train_s_per_iter": trn, "overall_env_steps_per_s": per_it / (roll + trn),
                               "mean_reward_last": hist[-1]["mean_reward"], "wall_s": dt,

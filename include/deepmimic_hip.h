@@ -207,6 +207,11 @@ int dm_linear_wgrad(const float *dY, const float *X, float *dW, float *db, int B
 int dm_ppo_gather(const long long *idx, int B, const float *obs, int D, const float *act, int A, const float *adv,
                   const float *ret, const float *logp, float *o_obs, float *o_act, float *o_adv, float *o_ret, float *o_logp,
                   void *stream);
+/* the same for a bf16 rollout buffer (PPO(buffer_dtype=torch.bfloat16), BASELINE config 5): obs / act are bf16 arrays (2-byte
+ * aligned, nothing more), widened exactly into the fp32 minibatch; adv / ret / logp as above.  D, A <= 1024. */
+int dm_ppo_gather_bf16(const long long *idx, int B, const unsigned short *obs, int D, const unsigned short *act, int A,
+                       const float *adv, const float *ret, const float *logp, float *o_obs, float *o_act, float *o_adv, float *o_ret,
+                       float *o_logp, void *stream);
 
 /* torch.nn.utils.clip_grad_norm_(max_norm) + torch.optim.Adam.step() [EXT, as used by SB3's PPO.train] on one flat
  * parameter / gradient / moment buffer of n floats.  state2 = {scratch, step count, DM_ADAM_PARTIALS partial sums} on the
@@ -233,6 +238,17 @@ typedef struct DmGatherSpec {
 int dm_flat_adam_step_gather(float *p, const float *g, float *m, float *v, int n, float lr, float beta1, float beta2, float eps,
                              float max_norm, float grad_scale, float *state2, int state2_floats, int begin, const DmGatherSpec *next,
                              void *stream);
+/* the same with the next minibatch gathered from a bf16 rollout buffer (dm_ppo_gather_bf16 as the extra blocks); next is required.
+ * The Adam half is the launch pair of dm_flat_adam_step_gather: same bits in p / m / v. */
+typedef struct DmGatherSpecBf16 {
+  const long long *idx; int B, D, A, reserved;
+  const unsigned short *obs, *act;
+  const float *adv, *ret, *logp;
+  float *o_obs, *o_act, *o_adv, *o_ret, *o_logp;
+} DmGatherSpecBf16;
+int dm_flat_adam_step_gather_bf16(float *p, const float *g, float *m, float *v, int n, float lr, float beta1, float beta2, float eps,
+                                  float max_norm, float grad_scale, float *state2, int state2_floats, int begin,
+                                  const DmGatherSpecBf16 *next, void *stream);
 
 /* out[o] += sum_b Y[b][o] for a row-major [B x O] matrix (out zeroed by the caller, stream-ordered): the bias gradient of the
  * nn.Linear layers of PPO.train [EXT] whose weight gradient stays on the library GEMM (layers beyond 256 units). */
@@ -259,6 +275,12 @@ int dm_policy_sample(const float *mean, const float *log_std, int N, int A, unsi
 int dm_rollout_store(int N, int D, int A, const float *last_obs, const float *act, const float *val, const float *logp,
                      const float *rew, const unsigned char *done, const float *new_obs, float *b_obs, float *b_act, float *b_val,
                      float *b_logp, float *b_rew, float *b_done, float *last_obs_out, unsigned *counter, void *stream);
+/* dm_rollout_store into a bf16 rollout buffer: b_obs / b_act are bf16 rows (2-byte aligned), written round-to-nearest-even as
+ * torch.Tensor.to(torch.bfloat16) does (NaN -> 0x7FC0); the fp32 outputs, last_obs_out and the counter as above. */
+int dm_rollout_store_bf16(int N, int D, int A, const float *last_obs, const float *act, const float *val, const float *logp,
+                          const float *rew, const unsigned char *done, const float *new_obs, unsigned short *b_obs,
+                          unsigned short *b_act, float *b_val, float *b_logp, float *b_rew, float *b_done, float *last_obs_out,
+                          unsigned *counter, void *stream);
 
 /* What follows the T env steps of a rollout, as one call on `stream` (capturable; csrc/dm_ppo.hip): rew / done / val are the
  * [T, N] rollout arrays (done: unsigned char when done_is_u8, float otherwise; done[t] is the flag step t returned), last_val [N].
@@ -294,6 +316,13 @@ int dm_policy_forward(const float *obs, int N, int D, int H1, int H2, int A, con
                       const float *vf_b3, const float *log_std, unsigned long long seed, const unsigned *counter,
                       unsigned draw_offset, int deterministic, const float *lo, const float *hi, float *mean_out, float *act,
                       float *act_env, float *logp, float *val, float *obs_copy, void *stream);
+/* dm_policy_forward for a bf16 rollout buffer: act and obs_copy are bf16 rows (2-byte aligned), narrowed at the store
+ * (round to nearest even, NaN -> 0x7FC0); mean_out / act_env / logp / val are bit for bit those of dm_policy_forward. */
+int dm_policy_forward_bf16(const float *obs, int N, int D, int H1, int H2, int A, const float *pi_packed, const float *pi_b1,
+                           const float *pi_b2, const float *pi_b3, const float *vf_packed, const float *vf_b1, const float *vf_b2,
+                           const float *vf_b3, const float *log_std, unsigned long long seed, const unsigned *counter,
+                           unsigned draw_offset, int deterministic, const float *lo, const float *hi, float *mean_out,
+                           unsigned short *act, float *act_env, float *logp, float *val, unsigned short *obs_copy, void *stream);
 
 /* One PPO minibatch gradient of SB3's MlpPolicy with two hidden layers (net_arch [H1, H2], tanh, separate policy / value
  * trunks) in three launches (csrc/dm_ppo_mlp.hip): what zero_grad + evaluate_actions + the dm_ppo_loss loss + backward
