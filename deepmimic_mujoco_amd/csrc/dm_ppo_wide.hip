@@ -15,7 +15,7 @@
 //   3. wide_wgrad_kernel   dW = dZ^T X of all six layers: the chain leaves its activations and pre-activation gradients TRANSPOSED
 //                          (features x batch) in the same fragment order, written straight from the accumulator registers (four
 //                          consecutive batch rows of a column are 8 bytes of a fragment); a workgroup of four waves owns four
-//                          32 x 32 tiles of dW, the waves split the batch and meet in LDS (plain stores on wide nets, split-K
+//                          32 x 32 tiles of dW, the waves split the batch and meet in LDS (plain adds on wide nets, split-K
 //                          with fp32 atomics only on narrow ones); the bias gradients of wide nets come from one more MFMA per
 //                          k-step against a fragment of ones; block 0 sums the loss partials                                 (1 launch)
 // Fragment order of a matrix M[N][K] (N % 32 == 0, K % 16 == 0) that feeds v_mfma_f32_32x32x16_bf16 as the operand with row / column
@@ -495,7 +495,7 @@ __global__ void __launch_bounds__(WIDE_THREADS) wide_fwdbwd_kernel(WideArgs a) {
 // XT = X^T (I x B): a wave's fragment load is 1 KB of consecutive bytes, the k-steps of a tile follow each other.  A workgroup of
 // four waves owns four 32 x 32 tiles of dW — 64 x 64 (RO = CI = 2), or 32 x 128 for the heads (RO = 1) — and the whole batch (or
 // 1 / splitk of it on small nets): every wave accumulates all four tiles over its quarter of the batch rows, the four partial
-// blocks meet in LDS (64 KB: two workgroups per CU) and each wave finishes one tile — a plain store when splitk == 1: no atomics,
+// blocks meet in LDS (64 KB: two workgroups per CU) and each wave finishes one tile — added to dW by its one owner when splitk == 1: no atomics,
 // fixed summation order.  Measured on the way (us per optimizer step of the [1024,512] learner, 4 096 rows):
 //   one wave per 32 x 128, four waves per workgroup re-reading X                                         216
 //   one wave per 128 x 128 (16 accumulators: 928 spilled VGPRs)                                            375
@@ -590,7 +590,7 @@ __device__ __forceinline__ void wide_wgrad_tile(const WideWgradJob &J, const int
       }
   }
   // the four partial blocks meet in LDS, four tiles at a time ([wave][tile][register][lane]: lane-contiguous, conflict-free); wave w
-  // then owns tile 4 ph + w: fixed summation order, and with splitk == 1 a plain store (no atomics, bit-reproducible gradients)
+  // then owns tile 4 ph + w: fixed summation order, and with splitk == 1 a plain add by the tile's one owner (no atomics, bit-reproducible gradients)
 #pragma unroll
   for (int ph = 0; ph < NT / 4; ph++) {
     if (ph) __syncthreads();
@@ -601,9 +601,18 @@ __device__ __forceinline__ void wide_wgrad_tile(const WideWgradJob &J, const int
 #pragma unroll
       for (int j = 0; j < 16; j++) wl[((wave * 4 + tt) << 10) + j * 64 + lane] = acc[t / CI][t % CI][j];
     }
-    __syncthreads();
     const int t = 4 * ph + wave, p = t / CI, q = t % CI;
-    if ((i0 + 32 * q + r) < J.I) {
+    const bool live = (i0 + 32 * q + r) < J.I;
+    // gradients are ACCUMULATED (deepmimic_hip.h), also where a tile has one owner: its present values are requested before the
+    // barrier, so the round trip passes under the LDS exchange
+    float old[16];
+#pragma unroll
+    for (int j = 0; j < 16; j++) {
+      const int row = o0 + 32 * p + wide_row(j, h);
+      old[j] = (J.splitk == 1 && live && row < J.O) ? J.dW[(size_t)row * J.ldw + i0 + 32 * q + r] : 0.f;
+    }
+    __syncthreads();
+    if (live) {
 #pragma unroll
       for (int j = 0; j < 16; j++) {
         float v = 0.f;
@@ -612,7 +621,7 @@ __device__ __forceinline__ void wide_wgrad_tile(const WideWgradJob &J, const int
         const int row = o0 + 32 * p + wide_row(j, h);
         if (row < J.O) {
           float *dst = &J.dW[(size_t)row * J.ldw + i0 + 32 * q + r];
-          if (J.splitk == 1) *dst = v; else atomicAdd(dst, v);
+          if (J.splitk == 1) *dst = old[j] + v; else atomicAdd(dst, v);
         }
       }
     }
