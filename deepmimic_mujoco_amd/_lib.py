@@ -49,15 +49,21 @@ class DmConfig(C.Structure):
 INTEGRATORS = {None: 0, "model": 0, "Euler": 1, "euler": 1, "RK4": 2, "rk4": 2}   # DM_CFG_INT_*
 
 
-class DmPpoMlpStep(C.Structure):
-    """include/deepmimic_hip.h: DmPpoMlpStep"""
+class DmPpoStepHead(C.Structure):
+    """The fields DmPpoMlpStep and DmPpoWideStep (include/deepmimic_hip.h) share, B through g_log_std.  It ends on a pointer, so it
+    has no tail padding and a derived struct's own fields follow at the offsets the header gives them."""
     _fields_ = [("B", C.c_int32), ("D", C.c_int32), ("H1", C.c_int32), ("H2", C.c_int32), ("A", C.c_int32),
                 ("normalize_advantage", C.c_int32), ("clip_range", C.c_float), ("vf_coef", C.c_float), ("ent_coef", C.c_float),
                 ("reserved", C.c_int32),
                 ("obs", C.c_void_p), ("act", C.c_void_p), ("adv", C.c_void_p), ("ret", C.c_void_p), ("old_logp", C.c_void_p),
                 ("log_std", C.c_void_p),
                 ("W", (C.c_void_p * 3) * 2), ("b", (C.c_void_p * 3) * 2), ("gW", (C.c_void_p * 3) * 2), ("gb", (C.c_void_p * 3) * 2),
-                ("g_log_std", C.c_void_p), ("out8", C.c_void_p), ("workspace", C.c_void_p), ("workspace_floats", C.c_longlong),
+                ("g_log_std", C.c_void_p)]
+
+
+class DmPpoMlpStep(DmPpoStepHead):
+    """include/deepmimic_hip.h: DmPpoMlpStep"""
+    _fields_ = [("out8", C.c_void_p), ("workspace", C.c_void_p), ("workspace_floats", C.c_longlong),
                 ("zero_ptr", C.c_void_p), ("zero_floats", C.c_longlong), ("adam_state2", C.c_void_p), ("loss_acc", C.c_void_p)]
 
 
@@ -72,16 +78,9 @@ class DmGatherSpecBf16(DmGatherSpec):
     """include/deepmimic_hip.h: DmGatherSpecBf16 — DmGatherSpec's layout; obs / act point at bf16 rows"""
 
 
-class DmPpoWideStep(C.Structure):
+class DmPpoWideStep(DmPpoStepHead):
     """include/deepmimic_hip.h: DmPpoWideStep"""
-    _fields_ = [("B", C.c_int32), ("D", C.c_int32), ("H1", C.c_int32), ("H2", C.c_int32), ("A", C.c_int32),
-                ("normalize_advantage", C.c_int32), ("clip_range", C.c_float), ("vf_coef", C.c_float), ("ent_coef", C.c_float),
-                ("reserved", C.c_int32),
-                ("obs", C.c_void_p), ("act", C.c_void_p), ("adv", C.c_void_p), ("ret", C.c_void_p), ("old_logp", C.c_void_p),
-                ("log_std", C.c_void_p),
-                ("W", (C.c_void_p * 3) * 2), ("b", (C.c_void_p * 3) * 2), ("gW", (C.c_void_p * 3) * 2), ("gb", (C.c_void_p * 3) * 2),
-                ("g_log_std", C.c_void_p),
-                ("wpk", C.c_void_p * 2), ("xbT", C.c_void_p), ("h1T", C.c_void_p * 2), ("dz1T", C.c_void_p * 2), ("h2T", C.c_void_p * 2),
+    _fields_ = [("wpk", C.c_void_p * 2), ("xbT", C.c_void_p), ("h1T", C.c_void_p * 2), ("dz1T", C.c_void_p * 2), ("h2T", C.c_void_p * 2),
                 ("dz2T", C.c_void_p * 2), ("dz3T", C.c_void_p * 2), ("part", C.c_void_p), ("stats8", C.c_void_p), ("out8", C.c_void_p),
                 ("zero_ptr", C.c_void_p), ("zero_floats", C.c_longlong), ("adam_state2", C.c_void_p), ("loss_acc", C.c_void_p)]
 
@@ -176,6 +175,17 @@ def load_library():
             getattr(L, name).restype = C.c_longlong if name in ("dm_policy_packed_floats", "dm_ppo_mlp_workspace_floats", "dm_ppo_wide_packed_elems", "dm_rollout_finish_workspace_bytes") else C.c_int
     _LIB = L
     return L
+
+
+def call(name, *args, device):
+    """Run the entry point ``name`` on ``device``'s current stream: a tensor argument becomes its ``data_ptr()``, anything else
+    (ints, floats, ``None``, ``byref(...)``) goes through ``argtypes`` as it is, the stream is appended as the last argument.
+    Raises ``RuntimeError("<name> failed (<rc>)")`` on a non-zero return."""
+    import torch
+    rc = getattr(load_library(), name)(*[a.data_ptr() if isinstance(a, torch.Tensor) else a for a in args],
+                                       torch.cuda.current_stream(device).cuda_stream)
+    if rc != 0:
+        raise RuntimeError("%s failed (%d)" % (name, rc))
 
 
 def default_config(**kw) -> DmConfig:

@@ -16,14 +16,18 @@ one process per GPU with ONE all-reduce of the flat gradient per optimizer step 
 """
 from __future__ import annotations
 
+import ctypes as C
 import math
+import os
 import time
 
 import numpy as np
 import torch
 import torch.distributed as dist
 from torch import nn
-from .streams import concurrent_streams
+
+from . import _lib
+from .rollout import EP_HIST, Collector, RolloutFinish, capture_graph, compute_gae, explained_variance64, route  # noqa: F401 (re-exported)
 
 
 class _HipLinearFn(torch.autograd.Function):
@@ -38,15 +42,10 @@ class _HipLinearFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gy):
-        import ctypes as C
-        from . import _lib
         x, w = ctx.saved_tensors
         gx = gy @ w if ctx.needs_input_grad[0] else None
         gy = gy.contiguous()
         arena = getattr(ctx.mod, "_grad_arena", None)    # (gw, gb) views of one flat buffer zeroed once per step
-        p = lambda t: C.c_void_p(t.data_ptr())
-        stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-        L = _lib.load_library()
         if max(w.shape) > 256 and min(w.shape) > 128:
             # large square-ish layers: dW on the library GEMM, written straight into the arena (no autograd-owned gradient, so
             # no copy into the flat buffer afterwards), db by dm_colsum.  Skinny layers of a big net (1024 x 67, 28 x 512,
@@ -57,18 +56,14 @@ class _HipLinearFn(torch.autograd.Function):
             else:
                 gw = gy.t() @ x
                 gb = torch.zeros(w.shape[0], device=w.device, dtype=w.dtype)
-            rc = L.dm_colsum(p(gy), x.shape[0], w.shape[0], p(gb), stream)
-            if rc != 0:
-                raise RuntimeError("dm_colsum failed (%d)" % rc)
+            _lib.call("dm_colsum", gy, x.shape[0], w.shape[0], gb, device=x.device)
             return (gx, None, None, None) if arena is not None else (gx, gw, gb, None)
         if arena is not None:
             gw, gb = arena
         else:
             gw = torch.zeros_like(w)
             gb = torch.zeros(w.shape[0], device=w.device, dtype=w.dtype)
-        rc = L.dm_linear_wgrad(p(gy), p(x), p(gw), p(gb), x.shape[0], w.shape[0], w.shape[1], stream)
-        if rc != 0:
-            raise RuntimeError("dm_linear_wgrad failed (%d)" % rc)
+        _lib.call("dm_linear_wgrad", gy, x, gw, gb, x.shape[0], w.shape[0], w.shape[1], device=x.device)
         if arena is not None:
             # the gradients already sit in the optimizer's flat buffer: handing views to autograd would make
             # AccumulateGrad clone them (a view cannot be stolen) and the optimizer copy them back — 2 copies per tensor
@@ -110,16 +105,10 @@ class _HipLinearTanhFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w, b, mod):
-        import ctypes as C
-        from . import _lib
         first = x.shape[1] <= 128 and not x.requires_grad
         if first:
             y = torch.empty(x.shape[0], w.shape[0], device=x.device, dtype=torch.float32)
-            rc = _lib.load_library().dm_linear_tanh(C.c_void_p(x.data_ptr()), C.c_void_p(w.data_ptr()), C.c_void_p(b.data_ptr()),
-                                                    C.c_void_p(y.data_ptr()), x.shape[0], w.shape[0], x.shape[1],
-                                                    C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream))
-            if rc != 0:
-                raise RuntimeError("dm_linear_tanh failed (%d)" % rc)
+            _lib.call("dm_linear_tanh", x, w, b, y, x.shape[0], w.shape[0], x.shape[1], device=x.device)
         else:
             y = torch.addmm(b, x, w.t()).tanh_()
         ctx.save_for_backward(x, w, y)
@@ -128,23 +117,14 @@ class _HipLinearTanhFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gy):
-        import ctypes as C
-        from . import _lib
         x, w, y = ctx.saved_tensors
         gw, gb = ctx.mod._grad_arena
         gy = gy.contiguous()
-        p = lambda t: C.c_void_p(t.data_ptr())
-        stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-        L = _lib.load_library()
         if ctx.first:
-            rc = L.dm_tanh_linear_wgrad(p(gy), p(y), p(x), p(gw), p(gb), x.shape[0], w.shape[0], w.shape[1], stream)
-            if rc != 0:
-                raise RuntimeError("dm_tanh_linear_wgrad failed (%d)" % rc)
+            _lib.call("dm_tanh_linear_wgrad", gy, y, x, gw, gb, x.shape[0], w.shape[0], w.shape[1], device=x.device)
             return None, None, None, None
         gz = torch.empty_like(gy)
-        rc = L.dm_tanh_bwd_colsum(p(gy), p(y), p(gz), p(gb), x.shape[0], w.shape[0], stream)
-        if rc != 0:
-            raise RuntimeError("dm_tanh_bwd_colsum failed (%d)" % rc)
+        _lib.call("dm_tanh_bwd_colsum", gy, y, gz, gb, x.shape[0], w.shape[0], device=x.device)
         torch.mm(gz.t(), x, out=gw)
         gx = gz @ w if ctx.needs_input_grad[0] else None
         return gx, None, None, None
@@ -238,180 +218,152 @@ class MlpPolicy(nn.Module):
         return self.value_net(self.vf(obs)).squeeze(-1)
 
 
+def two_hidden_layers(policy):
+    """(pi_layers, vf_layers, D, H1, H2, A) of an ``MlpPolicy`` with two hidden layers per trunk — the three linear layers of each
+    trunk with its head, and the sizes the fused kernels are built for — or None if ``policy`` is not one."""
+    if not isinstance(policy, MlpPolicy):
+        return None
+    pi, vf = ([m for m in seq if isinstance(m, nn.Linear)] for seq in (policy.pi, policy.vf))
+    if len(pi) != 2 or len(vf) != 2:
+        return None
+    return (pi + [policy.action_net], vf + [policy.value_net], pi[0].in_features, pi[0].out_features, pi[1].out_features,
+            policy.action_net.out_features)
+
+
 class FusedPolicyForward:
     """``dm_policy_forward`` (csrc/dm_policy.hip) for an ``MlpPolicy`` with two hidden layers: both trunks, the sampling
     head and the policy-side rollout-buffer writes as one launch.  ``pack()`` re-orders the weights into MFMA operand
     order and must be called again after the weights changed (once per ``collect_rollouts``)."""
 
     def __init__(self, policy, device):
-        from . import _lib
-        self.lib = _lib.load_library()
         self.policy, self.device = policy, device
-        lin = lambda seq: [m for m in seq if isinstance(m, nn.Linear)]
-        self.pi, self.vf = lin(policy.pi) + [policy.action_net], lin(policy.vf) + [policy.value_net]
-        self.D, self.H1, self.H2, self.A = self.pi[0].in_features, self.pi[0].out_features, self.pi[1].out_features, self.pi[2].out_features
-        n = int(self.lib.dm_policy_packed_floats(self.D, self.H1, self.H2, self.A))
+        self.pi, self.vf, self.D, self.H1, self.H2, self.A = two_hidden_layers(policy)
+        n = int(_lib.load_library().dm_policy_packed_floats(self.D, self.H1, self.H2, self.A))
         if n <= 0:
             raise ValueError("dm_policy_forward does not support this net")
         self.packed = [torch.zeros(n, device=device), torch.zeros(n, device=device)]
 
     @staticmethod
     def supported(policy, device):
-        if device.type != "cuda" or not isinstance(policy, MlpPolicy):
+        net = two_hidden_layers(policy)
+        if device.type != "cuda" or net is None:
             return False
-        lin = [m for m in policy.pi if isinstance(m, nn.Linear)]
-        if len(lin) != 2 or len([m for m in policy.vf if isinstance(m, nn.Linear)]) != 2:
-            return False
-        h1, h2, a, d = lin[0].out_features, lin[1].out_features, policy.action_net.out_features, lin[0].in_features
+        pi, _, d, h1, h2, a = net
         lds = 32 * (h1 + 4 + max(((d + 7) // 8) * 8 + 4, 132)) * 4
         return h1 % 32 == 0 and h2 % 32 == 0 and a <= 32 and lds <= 160 * 1024 and all(
-            m.weight.dtype == torch.float32 and m.weight.is_contiguous() for m in lin)
-
-    def _stream(self):
-        import ctypes as C
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            m.weight.dtype == torch.float32 and m.weight.is_contiguous() for m in pi[:2])
 
     def pack(self):
-        import ctypes as C
-        p = lambda t: C.c_void_p(t.data_ptr())
         for layers, out, a in ((self.pi, self.packed[0], self.A), (self.vf, self.packed[1], 1)):
-            rc = self.lib.dm_policy_pack(p(layers[0].weight), p(layers[1].weight), p(layers[2].weight), self.D, self.H1, self.H2, a,
-                                         p(out), self._stream())
-            if rc != 0:
-                raise RuntimeError("dm_policy_pack failed (%d)" % rc)
+            _lib.call("dm_policy_pack", layers[0].weight, layers[1].weight, layers[2].weight, self.D, self.H1, self.H2, a, out,
+                      device=self.device)
 
     def __call__(self, obs, seed, counter, draw_offset, lo, hi, act, act_env, logp, val, obs_copy=None, mean_out=None,
                  deterministic=False):
-        import ctypes as C
-        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
         pi, vf = self.pi, self.vf
         # the storage type of the two rollout-buffer outputs picks the entry point (PPO(buffer_dtype=...)); all else is fp32
         if act.dtype not in (torch.float32, torch.bfloat16) or (obs_copy is not None and obs_copy.dtype != act.dtype):
             raise ValueError("dm_policy_forward stores act / obs_copy as fp32 or bf16, both of one type")
-        entry = self.lib.dm_policy_forward_bf16 if act.dtype == torch.bfloat16 else self.lib.dm_policy_forward
-        rc = entry(
-            p(obs), obs.shape[0], self.D, self.H1, self.H2, self.A, p(self.packed[0]), p(pi[0].bias), p(pi[1].bias), p(pi[2].bias),
-            p(self.packed[1]), p(vf[0].bias), p(vf[1].bias), p(vf[2].bias), p(self.policy.log_std), C.c_uint64(seed), p(counter),
-            C.c_uint32(draw_offset), int(bool(deterministic)), p(lo), p(hi), p(mean_out), p(act), p(act_env), p(logp), p(val),
-            p(obs_copy), self._stream())
-        if rc != 0:
-            raise RuntimeError("dm_policy_forward failed (%d)" % rc)
+        _lib.call("dm_policy_forward_bf16" if act.dtype == torch.bfloat16 else "dm_policy_forward",
+                  obs, obs.shape[0], self.D, self.H1, self.H2, self.A, self.packed[0], pi[0].bias, pi[1].bias, pi[2].bias,
+                  self.packed[1], vf[0].bias, vf[1].bias, vf[2].bias, self.policy.log_std, seed, counter, draw_offset,
+                  int(bool(deterministic)), lo, hi, mean_out, act, act_env, logp, val, obs_copy, device=self.device)
 
 
-class FusedMlpGrad:
-    """``dm_ppo_mlp_grad`` (csrc/dm_ppo_mlp.hip): loss and every gradient of one PPO minibatch for an ``MlpPolicy`` with
-    two hidden layers of at most 256 units, in three launches, written into the flat gradient arena of ``FlatAdam``
-    (which the caller zeroes).  Returns the loss as a view of the device-side ``out8`` record."""
+class _FusedGrad:
+    """What ``FusedMlpGrad`` and ``WideMlpGrad`` share: the head of their step structs (``_lib.DmPpoStepHead``: sizes, weights and
+    biases, their slices of the flat gradient arena) and the call of one minibatch.  A subclass names its entry point in ``entry``,
+    allocates its buffers, fills the tail of ``st`` and leaves the 8-float loss record in ``out8``."""
 
-    def __init__(self, policy, opt, B, loss_acc=None, fold=True):
-        import ctypes as C
-        from . import _lib
-        self.lib, self.C, self.St = _lib.load_library(), C, _lib.DmPpoMlpStep
-        lin = lambda seq: [m for m in seq if isinstance(m, nn.Linear)]
-        pi, vf = lin(policy.pi) + [policy.action_net], lin(policy.vf) + [policy.value_net]
-        dev = policy.log_std.device
-        D, H1, H2, A = pi[0].in_features, pi[0].out_features, pi[1].out_features, pi[2].out_features
-        n = int(self.lib.dm_ppo_mlp_workspace_floats(B, D, H1, H2, A))
-        if n <= 0:
-            raise ValueError("dm_ppo_mlp_grad does not support this net / minibatch")
-        self.ws = torch.zeros(n, device=dev)
-        self.out8 = torch.zeros(8, device=dev)
+    entry = None
+
+    def _head(self, st, policy, opt, B):
+        pi, vf, st.D, st.H1, st.H2, st.A = two_hidden_layers(policy)
         grad = {id(p): g for p, g in zip(opt.params, opt.slices)}
-        st = self.St()
-        st.B, st.D, st.H1, st.H2, st.A = B, D, H1, H2, A
+        st.B = B
         for t, layers in enumerate((pi, vf)):
             for l, m in enumerate(layers):
                 st.W[t][l], st.b[t][l] = m.weight.data_ptr(), m.bias.data_ptr()
                 st.gW[t][l], st.gb[t][l] = grad[id(m.weight)].data_ptr(), grad[id(m.bias)].data_ptr()
         st.log_std, st.g_log_std = policy.log_std.data_ptr(), grad[id(policy.log_std)].data_ptr()
+        self.st, self.B, self.dev = st, B, policy.log_std.device
+
+    def __call__(self, obs, act, adv, ret, old_logp, clip_range, vf_coef, ent_coef, normalize):
+        st = self.st
+        for t in (obs, act, adv, ret, old_logp):
+            assert t.is_contiguous() and t.dtype == torch.float32 and t.shape[0] == self.B
+        st.obs, st.act, st.adv, st.ret, st.old_logp = (t.data_ptr() for t in (obs, act, adv, ret, old_logp))
+        st.clip_range, st.vf_coef, st.ent_coef, st.normalize_advantage = clip_range, vf_coef, ent_coef, int(bool(normalize))
+        _lib.call(self.entry, C.byref(st), device=self.dev)
+        return self.out8[0]
+
+
+class FusedMlpGrad(_FusedGrad):
+    """``dm_ppo_mlp_grad`` (csrc/dm_ppo_mlp.hip): loss and every gradient of one PPO minibatch for an ``MlpPolicy`` with
+    two hidden layers of at most 256 units, in three launches, written into the flat gradient arena of ``FlatAdam``
+    (which the caller zeroes).  Returns the loss as a view of the device-side ``out8`` record."""
+
+    entry = "dm_ppo_mlp_grad"
+
+    def __init__(self, policy, opt, B, loss_acc=None, fold=True):
+        st = _lib.DmPpoMlpStep()
+        self._head(st, policy, opt, B)
+        dev = self.dev
+        n = int(_lib.load_library().dm_ppo_mlp_workspace_floats(B, st.D, st.H1, st.H2, st.A))
+        if n <= 0:
+            raise ValueError("dm_ppo_mlp_grad does not support this net / minibatch")
+        self.ws = torch.zeros(n, device=dev)
+        self.out8 = torch.zeros(8, device=dev)
         st.out8, st.workspace, st.workspace_floats = self.out8.data_ptr(), self.ws.data_ptr(), n
-        st.reserved = int(__import__("os").environ.get("DM_WGRAD_SPLITK", "0"))      # 0: library default (experiments)
+        st.reserved = int(os.environ.get("DM_WGRAD_SPLITK", "0"))      # 0: library default (experiments)
         self.folded = bool(fold)
         if fold:    # the launch also clears the gradient arena, does Adam's begin and keeps the running loss sum
             self.loss_acc = loss_acc if loss_acc is not None else torch.zeros(2, device=dev)
             st.zero_ptr, st.zero_floats = opt.flat_g.data_ptr(), opt.n
             st.adam_state2, st.loss_acc = opt.state2.data_ptr(), self.loss_acc.data_ptr()
-        self.st, self.B, self.dev = st, B, dev
 
     @staticmethod
     def supported(policy, B):
-        if not isinstance(policy, MlpPolicy) or policy.log_std.device.type != "cuda":
+        net = two_hidden_layers(policy)
+        if net is None or policy.log_std.device.type != "cuda":
             return False
-        lin = [m for m in policy.pi if isinstance(m, nn.Linear)]
-        if len(lin) != 2 or len([m for m in policy.vf if isinstance(m, nn.Linear)]) != 2:
-            return False
-        h1, h2 = lin[0].out_features, lin[1].out_features
-        return (B >= 64 and B % 64 == 0 and h1 % 32 == 0 and h2 % 32 == 0 and h1 <= 256 and h2 <= 256
-                and policy.action_net.out_features <= 32)
-
-    def __call__(self, obs, act, adv, ret, old_logp, clip_range, vf_coef, ent_coef, normalize):
-        st = self.st
-        for t in (obs, act, adv, ret, old_logp):
-            assert t.is_contiguous() and t.dtype == torch.float32 and t.shape[0] == self.B
-        st.obs, st.act, st.adv, st.ret, st.old_logp = (t.data_ptr() for t in (obs, act, adv, ret, old_logp))
-        st.clip_range, st.vf_coef, st.ent_coef, st.normalize_advantage = clip_range, vf_coef, ent_coef, int(bool(normalize))
-        rc = self.lib.dm_ppo_mlp_grad(self.C.byref(st), self.C.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream))
-        if rc != 0:
-            raise RuntimeError("dm_ppo_mlp_grad failed (%d)" % rc)
-        return self.out8[0]
+        h1, h2, a = net[3:]
+        return B >= 64 and B % 64 == 0 and h1 % 32 == 0 and h2 % 32 == 0 and h1 <= 256 and h2 <= 256 and a <= 32
 
 
-class WideMlpGrad:
+class WideMlpGrad(_FusedGrad):
     """One minibatch gradient of the WIDE net ([1024,512]-class, the net BASELINE configs 3-5 name) with bf16 matrix-pipe products
     (`dm_ppo_wide_grad`, csrc/dm_ppo_wide.hip): weights -> bf16, the fused forward / loss / input-gradient chain of both trunks, the
     six weight gradients — three launches.  fp32 master weights, fp32 loss, gradients and Adam.  Leaves every gradient in
     ``opt.flat_g`` (cleared by the first launch, which also performs Adam's begin) and adds the loss to ``loss_acc``."""
 
+    entry = "dm_ppo_wide_grad"
+
     def __init__(self, policy, opt, B, loss_acc):
-        import ctypes as C
-        from . import _lib
-        self.lib, self.C = _lib.load_library(), C
-        lin = lambda seq: [m for m in seq if isinstance(m, nn.Linear)]
-        pi, vf = lin(policy.pi) + [policy.action_net], lin(policy.vf) + [policy.value_net]
-        dev = policy.log_std.device
-        D, H1, H2, A = pi[0].in_features, pi[0].out_features, pi[1].out_features, pi[2].out_features
-        Dp = int(self.lib.dm_ppo_wide_dp(D))
+        st = _lib.DmPpoWideStep()
+        self._head(st, policy, opt, B)
+        dev, L = self.dev, _lib.load_library()
+        D, H1, H2 = st.D, st.H1, st.H2
+        Dp = int(L.dm_ppo_wide_dp(D))
         bf = lambda *shape: torch.zeros(*shape, device=dev, dtype=torch.bfloat16)
-        npk = int(self.lib.dm_ppo_wide_packed_elems(D, H1, H2))
+        npk = int(L.dm_ppo_wide_packed_elems(D, H1, H2))
         self.buf = dict(wpk=[bf(npk), bf(npk)], xbT=bf((Dp + 31) // 32 * 32, B), h1T=[bf(H1, B), bf(H1, B)], dz1T=[bf(H1, B), bf(H1, B)], h2T=[bf(H2, B), bf(H2, B)],
                         dz2T=[bf(H2, B), bf(H2, B)], dz3T=[bf(32, B), bf(32, B)], part=torch.zeros(2 * (B // 32) * 40, device=dev),
                         stats8=torch.zeros(8, device=dev), out8=torch.zeros(8, device=dev))
-        grad = {id(p): g for p, g in zip(opt.params, opt.slices)}
-        st = _lib.DmPpoWideStep()
-        st.B, st.D, st.H1, st.H2, st.A = B, D, H1, H2, A
-        for t, layers in enumerate((pi, vf)):
-            for l, m in enumerate(layers):
-                st.W[t][l], st.b[t][l] = m.weight.data_ptr(), m.bias.data_ptr()
-                st.gW[t][l], st.gb[t][l] = grad[id(m.weight)].data_ptr(), grad[id(m.bias)].data_ptr()
+        self.out8 = self.buf["out8"]
+        for t in range(2):
             for k in ("wpk", "h1T", "dz1T", "h2T", "dz2T", "dz3T"):
                 getattr(st, k)[t] = self.buf[k][t].data_ptr()
         st.xbT, st.part, st.stats8, st.out8 = (self.buf[k].data_ptr() for k in ("xbT", "part", "stats8", "out8"))
-        st.log_std, st.g_log_std = policy.log_std.data_ptr(), grad[id(policy.log_std)].data_ptr()
         st.zero_ptr, st.zero_floats = opt.flat_g.data_ptr(), opt.n
         st.adam_state2, st.loss_acc = opt.state2.data_ptr(), loss_acc.data_ptr()
-        self.st, self.B, self.dev = st, B, dev
 
     @staticmethod
     def supported(policy, B):
-        if not isinstance(policy, MlpPolicy) or policy.log_std.device.type != "cuda":
+        net = two_hidden_layers(policy)
+        if net is None or policy.log_std.device.type != "cuda":
             return False
-        lin = [m for m in policy.pi if isinstance(m, nn.Linear)]
-        if len(lin) != 2 or len([m for m in policy.vf if isinstance(m, nn.Linear)]) != 2:
-            return False
-        from . import _lib
-        return bool(_lib.load_library().dm_ppo_wide_supported(int(B), lin[0].in_features, lin[0].out_features, lin[1].out_features,
-                                                              policy.action_net.out_features))
-
-    def __call__(self, obs, act, adv, ret, old_logp, clip_range, vf_coef, ent_coef, normalize):
-        st = self.st
-        for t in (obs, act, adv, ret, old_logp):
-            assert t.is_contiguous() and t.dtype == torch.float32 and t.shape[0] == self.B
-        st.obs, st.act, st.adv, st.ret, st.old_logp = (t.data_ptr() for t in (obs, act, adv, ret, old_logp))
-        st.clip_range, st.vf_coef, st.ent_coef, st.normalize_advantage = clip_range, vf_coef, ent_coef, int(bool(normalize))
-        rc = self.lib.dm_ppo_wide_grad(self.C.byref(st), self.C.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream))
-        if rc != 0:
-            raise RuntimeError("dm_ppo_wide_grad failed (%d)" % rc)
-        return self.buf["out8"][0]
+        return bool(_lib.load_library().dm_ppo_wide_supported(int(B), *net[2:]))
 
 
 class ExtractedPolicy:
@@ -448,18 +400,11 @@ class FusedPPOLoss(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, mean, log_std, value, act, old_logp, adv, ret, clip_range, vf_coef, ent_coef, normalize):
-        from . import _lib
-        import ctypes as C
-        L = _lib.load_library()
         B, A = mean.shape
         b = FusedPPOLoss.buffers(B, A, mean.device)
         args = [t.detach().contiguous().float() for t in (mean, log_std, value, act, old_logp, adv, ret)]
-        p = lambda t: C.c_void_p(t.data_ptr())
-        rc = L.dm_ppo_loss(*[p(t) for t in args], B, A, float(clip_range), float(vf_coef), float(ent_coef),
-                           1 if normalize else 0, p(b["gm"]), p(b["gl"]), p(b["gv"]), p(b["out"]), p(b["scratch"]),
-                           C.c_void_p(torch.cuda.current_stream(mean.device).cuda_stream))
-        if rc != 0:
-            raise RuntimeError("dm_ppo_loss failed (%d)" % rc)
+        _lib.call("dm_ppo_loss", *args, B, A, float(clip_range), float(vf_coef), float(ent_coef), 1 if normalize else 0,
+                  b["gm"], b["gl"], b["gv"], b["out"], b["scratch"], device=mean.device)
         ctx.b = b
         ctx._keep = args
         return b["out"][0]
@@ -475,146 +420,14 @@ class FusedPPOLoss(torch.autograd.Function):
         writes d loss / d log_std into ``grad_log_std`` (e.g. the optimizer's arena slice).  The caller seeds the
         backward pass with ``torch.autograd.backward([mean, value], [gm, gv])``: no `g * grad` products, no gradient
         tensors handed back through a Function node (three multiplies, an add and a copy per step on the library path)."""
-        from . import _lib
-        import ctypes as C
         B, A = mean.shape
         b = FusedPPOLoss.buffers(B, A, mean.device)
         gl = grad_log_std if grad_log_std is not None else b["gl"]
         args = [t.detach() for t in (mean, log_std, value, act, old_logp, adv, ret)]
         assert all(t.is_contiguous() and t.dtype == torch.float32 for t in args)
-        p = lambda t: C.c_void_p(t.data_ptr())
-        rc = _lib.load_library().dm_ppo_loss(*[p(t) for t in args], B, A, float(clip_range), float(vf_coef), float(ent_coef),
-                                             1 if normalize else 0, p(b["gm"]), p(gl), p(b["gv"]), p(b["out"]), p(b["scratch"]),
-                                             C.c_void_p(torch.cuda.current_stream(mean.device).cuda_stream))
-        if rc != 0:
-            raise RuntimeError("dm_ppo_loss failed (%d)" % rc)
+        _lib.call("dm_ppo_loss", *args, B, A, float(clip_range), float(vf_coef), float(ent_coef), 1 if normalize else 0,
+                  b["gm"], gl, b["gv"], b["out"], b["scratch"], device=mean.device)
         return b["out"][0], b["gm"], b["gv"]
-
-
-def compute_gae(rewards, values, dones, last_values, gamma, lam):
-    """SB3 ``RolloutBuffer.compute_returns_and_advantage`` [EXT]: tensors [T, N]; dones[t] is the done
-    flag returned by step t (so the value after it is not bootstrapped)."""
-    T = rewards.shape[0]
-    adv = torch.zeros_like(rewards)
-    last = torch.zeros_like(last_values)
-    for t in reversed(range(T)):
-        next_v = last_values if t == T - 1 else values[t + 1]
-        nonterm = 1.0 - dones[t]
-        delta = rewards[t] + gamma * next_v * nonterm - values[t]
-        last = delta + gamma * lam * nonterm * last
-        adv[t] = last
-    return adv, adv + values
-
-
-EP_HIST = 100        # SB3: ep_info_buffer = deque(maxlen=100)
-
-
-def explained_variance64(values, returns):
-    """SB3's ``explained_variance(y_pred, y_true)`` = 1 - var(y_true - y_pred) / var(y_true) in fp64 (NaN when var(y_true) is 0)."""
-    y, v = np.asarray(returns, np.float64).reshape(-1), np.asarray(values, np.float64).reshape(-1)
-    vy = float(np.var(y))
-    return float("nan") if vy == 0.0 else 1.0 - float(np.var(y - v)) / vy
-
-
-class RolloutFinish:
-    """What follows the T env steps of a rollout: GAE, SB3's Monitor for the vec-env (per-env episode return / length that
-    persist across rollouts, the last 100 finished episodes) and the rollout statistics.  On the GPU this is ONE call of
-    ``dm_rollout_finish`` (csrc/dm_ppo.hip) on the current stream, capturable into a hipGraph, with all state on the device and
-    ``read()`` as the one small device-to-host copy; on the CPU ``compute_gae`` plus the same monitor in numpy.  Episodes are
-    numbered in (rollout, step, env) order, as SB3's ``_update_info_buffer`` meets them; returns are fp32 sums in step order."""
-
-    def __init__(self, T, N, device, gamma, gae_lambda):
-        self.T, self.N, self.device, self.gamma, self.gae_lambda = int(T), int(N), torch.device(device), float(gamma), float(gae_lambda)
-        self.on_gpu = self.device.type == "cuda"
-        if self.on_gpu:
-            from . import _lib
-            self._L = _lib.load_library()
-            # one arena = one host read: [0:16) the 8 fp64 statistics, [16:216) ep_hist [2, 100], [216] ep_count (uint32)
-            self.arena = torch.zeros(16 + 2 * EP_HIST + 8, device=self.device)
-            self.stats64 = self.arena[:16].view(torch.float64)
-            self.ep_hist = self.arena[16:16 + 2 * EP_HIST]
-            self.ep_count = self.arena[16 + 2 * EP_HIST:16 + 2 * EP_HIST + 1].view(torch.int32)
-            self.ep_acc = torch.zeros(2 * self.N, device=self.device)
-            self.work_bytes = int(self._L.dm_rollout_finish_workspace_bytes(self.T, self.N))
-            self.work = torch.zeros(self.work_bytes, dtype=torch.uint8, device=self.device)
-        else:
-            self._acc = np.zeros((2, self.N), np.float32)
-            self._hist = np.zeros((2, EP_HIST), np.float32)
-            self._count = 0
-            self._stats = np.zeros(8)
-
-    def reset(self):
-        """Forget every episode, finished or running (a loaded checkpoint carries no monitor state, as in SB3)."""
-        if self.on_gpu:
-            self.arena.zero_()
-            self.ep_acc.zero_()
-        else:
-            self._acc[:] = 0
-            self._hist[:] = 0
-            self._count = 0
-            self._stats[:] = 0
-
-    def __call__(self, rew, done, val, last_val, adv=None, ret=None):
-        """rew / val [T, N] fp32, done [T, N] uint8 or fp32, last_val [N] -> (adv, ret); advances the monitor by this rollout."""
-        T, N = self.T, self.N
-        assert tuple(rew.shape) == (T, N) and tuple(done.shape) == (T, N) and tuple(val.shape) == (T, N) and last_val.numel() == N
-        if not self.on_gpu:
-            adv_, ret_ = compute_gae(rew, val, done if done.dtype == torch.float32 else done.float(), last_val, self.gamma, self.gae_lambda)
-            self._monitor_numpy(rew.numpy(), done.numpy() != 0, val.numpy(), ret_.numpy())
-            if adv is not None:
-                adv.copy_(adv_); ret.copy_(ret_)
-                return adv, ret
-            return adv_, ret_
-        import ctypes as C
-        if adv is None:
-            adv, ret = torch.empty_like(rew), torch.empty_like(rew)
-        last_val = last_val.reshape(-1)
-        for t in (rew, val, last_val, adv, ret):
-            if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
-                raise ValueError("dm_rollout_finish takes contiguous fp32 device tensors")
-        if not (done.is_cuda and done.is_contiguous() and done.dtype in (torch.uint8, torch.float32)):
-            raise ValueError("dm_rollout_finish takes done flags as a contiguous uint8 or fp32 device tensor")
-        p = lambda t: C.c_void_p(t.data_ptr())
-        rc = self._L.dm_rollout_finish(T, N, p(rew), p(done), 1 if done.dtype == torch.uint8 else 0, p(val), p(last_val), self.gamma,
-                                       self.gae_lambda, p(adv), p(ret), p(self.ep_acc), p(self.ep_hist), p(self.ep_count),
-                                       p(self.stats64), p(self.work), self.work_bytes,
-                                       C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
-        if rc != 0:
-            raise RuntimeError("dm_rollout_finish failed (%d)" % rc)
-        return adv, ret
-
-    def _monitor_numpy(self, rew, fin, val, ret):
-        acc, one = self._acc, np.float32(1.0)
-        for t in range(self.T):
-            acc[0] += rew[t]
-            acc[1] += one
-            for e in np.nonzero(fin[t])[0]:                      # env order within the step
-                k = self._count % EP_HIST
-                self._hist[0, k], self._hist[1, k] = acc[0, e], acc[1, e]
-                self._count += 1
-            acc[:, fin[t]] = 0
-        y, d = ret.astype(np.float64), ret.astype(np.float64) - val.astype(np.float64)
-        vy, vd = float(np.var(y)), float(np.var(d))
-        self._stats[:] = (float(rew.astype(np.float64).sum()), float(fin.sum()), float("nan") if vy == 0.0 else 1.0 - vd / vy, vy, vd,
-                          float(rew.size), float(self._count), float(y.mean()))
-
-    def read(self):
-        """Statistics of the last rollout and the episode history, oldest episode first: one device-to-host copy on the GPU."""
-        if self.on_gpu:
-            host = self.arena.cpu()
-            st = host[:16].view(torch.float64).numpy()
-            hist = host[16:16 + 2 * EP_HIST].numpy().reshape(2, EP_HIST)
-            count = int(host[16 + 2 * EP_HIST:16 + 2 * EP_HIST + 1].view(torch.int32)[0]) & 0xFFFFFFFF
-        else:
-            st, hist, count = self._stats, self._hist, self._count
-        k = min(count, EP_HIST)
-        order = (np.arange(EP_HIST) + count) % EP_HIST if count >= EP_HIST else np.arange(k)       # slot of episode count - 100 first
-        ep_rew, ep_len = hist[0, order].copy(), hist[1, order].copy()
-        n = float(st[5]) if st[5] > 0 else 1.0
-        return dict(reward_sum=float(st[0]), dones=int(st[1]), n=int(st[5]), mean_reward=float(st[0]) / n, done_rate=float(st[1]) / n,
-                    explained_variance=float(st[2]), episodes=count, ep_returns=ep_rew, ep_lengths=ep_len,
-                    ep_rew_mean=float(np.mean(ep_rew.astype(np.float64))) if k else float("nan"),
-                    ep_len_mean=float(np.mean(ep_len.astype(np.float64))) if k else float("nan"))
 
 
 class FlatGradAllReduce:
@@ -733,15 +546,11 @@ class FlatAdam:
         """begin=False: state2 was prepared by dm_ppo_mlp_grad (adam_state2 fold) — two launches instead of three.
         gather_next = (flat, idx, out): the gather of the NEXT minibatch (rows idx of flat["obs" | "act" | "adv" | "ret" | "logp"] ->
         out[...]) rides on the norm launch (dm_flat_adam_step_gather): one launch less per optimizer step."""
-        import ctypes as C
-        from . import _lib
-        p = lambda t: C.c_void_p(t.data_ptr())
-        L = _lib.load_library()
-        common = (p(self.flat_p), p(self.flat_g), p(self.m), p(self.v), self.n, self.lr, self.betas[0], self.betas[1], self.eps,
-                  self.max_grad_norm, self.grad_scale, p(self.state2), int(self.state2.numel()))
-        stream = C.c_void_p(torch.cuda.current_stream(self.flat_p.device).cuda_stream)
+        common = (self.flat_p, self.flat_g, self.m, self.v, self.n, self.lr, self.betas[0], self.betas[1], self.eps,
+                  self.max_grad_norm, self.grad_scale, self.state2, int(self.state2.numel()))
+        dev = self.flat_p.device
         if gather_next is None:
-            rc = (L.dm_flat_adam_step if begin else L.dm_flat_adam_update)(*common, stream)
+            _lib.call("dm_flat_adam_step" if begin else "dm_flat_adam_update", *common, device=dev)
         else:
             flat, idx, out = gather_next
             assert idx.dtype == torch.int64 and idx.is_contiguous()
@@ -753,9 +562,8 @@ class FlatAdam:
             gs.idx, gs.B, gs.D, gs.A = idx.data_ptr(), int(idx.numel()), int(flat["obs"].shape[1]), int(flat["act"].shape[1])
             gs.obs, gs.act, gs.adv, gs.ret, gs.logp = (flat[k].data_ptr() for k in ("obs", "act", "adv", "ret", "logp"))
             gs.o_obs, gs.o_act, gs.o_adv, gs.o_ret, gs.o_logp = (out[k].data_ptr() for k in ("obs", "act", "adv", "ret", "logp"))
-            rc = (L.dm_flat_adam_step_gather_bf16 if kind == "bf16" else L.dm_flat_adam_step_gather)(*common, int(bool(begin)), C.byref(gs), stream)
-        if rc != 0:
-            raise RuntimeError("dm_flat_adam_step failed (%d)" % rc)
+            _lib.call("dm_flat_adam_step_gather_bf16" if kind == "bf16" else "dm_flat_adam_step_gather", *common, int(bool(begin)),
+                      C.byref(gs), device=dev)
         if self.flat_pb is not None:
             self.flat_pb.copy_(self.flat_p)
 
@@ -845,20 +653,14 @@ class PPO:
         self._last_obs = None
         self.stats = {}
         self._finish = None      # RolloutFinish (GAE + episode monitor + rollout statistics), made with the first rollout
+        self._collector = None   # rollout.Collector: every piece of rollout state, made with the first rollout
 
     # ------------------------------------------------------------------ rollout
-    def _rollout_finish(self):
-        """The rollout's tail, shared by every rollout path (the captured ones bake its device buffers into their graph)."""
-        if self._finish is None:
-            self._finish = RolloutFinish(self.n_steps, self.n_envs, self.device, self.gamma, self.gae_lambda)
-        return self._finish
-
-    def _rollout_stats(self):
-        """After the rollout (never inside it): one small read of what the finish left -> ``stats``."""
-        r = self._finish.read()
-        self.stats.update(mean_reward=r["mean_reward"], done_rate=r["done_rate"], ep_rew_mean=r["ep_rew_mean"], ep_len_mean=r["ep_len_mean"],
-                          episodes=r["episodes"], explained_variance=r["explained_variance"])
-        return r
+    def collector(self):
+        """The one ``rollout.Collector`` of this PPO (buffers, last observations, streams, draw counters, captured graph)."""
+        if self._collector is None:
+            self._collector = Collector(self)
+        return self._collector
 
     def ep_history(self):
         """(returns, lengths) of the last <= 100 finished episodes, oldest first (SB3's ``ep_info_buffer``)."""
@@ -867,301 +669,27 @@ class PPO:
         r = self._finish.read()
         return r["ep_returns"], r["ep_lengths"]
 
-    # ---- rollout-side fused kernels (csrc/dm_ppo.hip): policy head -> sampled / clamped action + logp, and the
-    # per-step stores into the rollout buffer, two launches instead of ~20 small PyTorch kernels per env step
     def _fused_rollout_ok(self):
-        # fp32 or bf16 storage of the buffer's obs / act (the kernels narrow at the store); anything else: the plain loop
+        """dm_policy_sample + dm_rollout_store can serve the step: fp32 or bf16 storage of the buffer's obs / act (the kernels narrow
+        at the store); anything else takes the plain step."""
         return (self.fused_rollout and self.device.type == "cuda" and self.buffer_dtype in (torch.float32, torch.bfloat16))
 
-    def _rollout_scratch(self, key):
-        sc = getattr(self, "_rsc", {})
-        if key not in sc:
-            n = key[0]
-            z = lambda *shape: torch.zeros(*shape, device=self.device)
-            sc[key] = dict(act=z(n, self.act_dim), act_env=z(n, self.act_dim), logp=z(n))
-            self._rsc = sc
-        if getattr(self, "_rctrs", None) is None:
-            # draw counters, advanced on the device: ONE PER SUB-BATCH — sub-batch chains run on their own streams (or as
-            # independent branches of a captured graph), so a shared counter bumped by one chain would be read by the
-            # others at unordered times (same noise at consecutive steps, non-reproducible rollouts)
-            self._rctrs = torch.zeros(max(16, int(getattr(self.env, "sub_batches", 1))), dtype=torch.int32, device=self.device)
-            self._rctr = self._rctrs[0:1]
-        return sc[key]
-
-    def _ctr(self, k):
-        return self._rctrs[k:k + 1]
-
-    def _policy_step_fused(self, obs, env_index=0):
-        """mean/value by the MLP (library GEMMs), then one launch for sample + logp + clamp."""
-        import ctypes as C
-        from . import _lib
-        n = obs.shape[0]
-        sc = self._rollout_scratch((n, env_index))
-        mean = self.policy.action_net(self.policy.pi(obs))
-        val = self.policy.value_net(self.policy.vf(obs)).squeeze(-1).contiguous()
-        p = lambda t: C.c_void_p(t.data_ptr())
-        rc = _lib.load_library().dm_policy_sample(p(mean.contiguous()), p(self.policy.log_std), n, self.act_dim,
-                                                  C.c_uint64(self._rollout_seed + 7919 * env_index), p(self._ctr(env_index)), p(self.act_lo),
-                                                  p(self.act_hi), p(sc["act"]), p(sc["act_env"]), p(sc["logp"]),
-                                                  C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
-        if rc != 0:
-            raise RuntimeError("dm_policy_sample failed (%d)" % rc)
-        return sc, val
-
-    def _store_fused(self, rb, t, sl, last, sc, val, out, bump, env_index=0):
-        import ctypes as C
-        from . import _lib
-        p = lambda x: C.c_void_p(x.data_ptr())
-        n = val.shape[0]
-        L = _lib.load_library()
-        if rb["obs"].dtype != rb["act"].dtype or rb["obs"].dtype not in (torch.float32, torch.bfloat16):
-            raise ValueError("dm_rollout_store files obs / act as fp32 or bf16, both of one type")
-        rc = (L.dm_rollout_store_bf16 if rb["obs"].dtype == torch.bfloat16 else L.dm_rollout_store)(
-            n, self.obs_dim, self.act_dim, p(last[sl]), p(sc["act"]), p(val), p(sc["logp"]), p(out["rew"]), p(out["done"]), p(out["obs"]),
-            p(rb["obs"][t, sl]), p(rb["act"][t, sl]), p(rb["val"][t, sl]), p(rb["logp"][t, sl]), p(rb["rew"][t, sl]),
-            p(rb["done"][t, sl]), p(last[sl]), p(self._ctr(env_index)) if bump else None,
-            C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
-        if rc != 0:
-            raise RuntimeError("dm_rollout_store failed (%d)" % rc)
-
-    # ---- one-launch policy side (csrc/dm_policy.hip): per env step dm_policy_forward + dm_step, nothing else
     def _fused_policy_ok(self):
+        """dm_policy_forward + dm_step can serve the step (csrc/dm_policy.hip): nothing else per env step."""
         return (self.fused_policy and self._fused_rollout_ok() and self.env is not None
                 and (hasattr(self.env, "engines") or hasattr(self.env, "engine"))
                 and FusedPolicyForward.supported(self.policy, self.device))
 
-    def _rollout_fused_policy(self):
-        """Rollout with two host calls per (sub-batch) step: ``dm_policy_forward`` reads the observations in place and
-        writes action / value / log-prob / observation copy straight into row t of the rollout buffer, ``dm_step``
-        writes reward and done flag into row t and the next observation over the one just consumed.  With
-        ``env.sub_batches`` > 1 every sub-batch runs on its own stream (the policy kernel of one fills the ramp-down of
-        the other's step kernel), host-driven or, with ``rollout_graph``, as one captured hipGraph of the T steps."""
-        env, T, N, dev = self.env, self.n_steps, self.n_envs, self.device
-        K = getattr(env, "sub_batches", 1)
-        engines = getattr(env, "engines", None) or [env.engine]
-        st = getattr(self, "_fp", None)
-        if st is None:
-            z = lambda *shape, dt=torch.float32: torch.zeros(*shape, device=dev, dtype=dt)
-            bd = self.buffer_dtype
-            rb = dict(obs=z(T, N, self.obs_dim, dt=bd), act=z(T, N, self.act_dim, dt=bd), rew=z(T, N), done_u8=z(T, N, dt=torch.uint8), val=z(T, N),
-                      logp=z(T, N), adv=z(T, N), ret=z(T, N), done=z(T, N))
-            last = (env.reset_tensor() if self._last_obs is None else self._last_obs).clone()
-            self._rollout_scratch((N, 0))
-            st = self._fp = dict(rb=rb, last=last, fwd=FusedPolicyForward(self.policy, dev), act_env=z(N, self.act_dim),
-                                 streams=concurrent_streams(dev, K) if K > 1 else None, graph=None)
-        rb, last, fwd = st["rb"], st["last"], st["fwd"]
-        finish = self._rollout_finish()
-        if self._last_obs is not None and self._last_obs.data_ptr() != last.data_ptr():
-            last.copy_(self._last_obs)
-
-        def sub_step(k, t):
-            sl = env.sub_slices[k] if K > 1 else slice(0, N)
-            fwd(last[sl], self._rollout_seed + 7919 * k, self._rctr, t, self.act_lo, self.act_hi, rb["act"][t, sl], st["act_env"][sl],
-                rb["logp"][t, sl], rb["val"][t, sl], obs_copy=rb["obs"][t, sl])
-            engines[k].step(st["act_env"][sl], dict(obs=last[sl], rew=rb["rew"][t, sl], done=rb["done_u8"][t, sl]))
-
-        def whole():
-            cur = torch.cuda.current_stream(dev)
-            fwd.pack()
-            if K == 1:
-                for t in range(T):
-                    sub_step(0, t)
-            else:
-                for s_ in st["streams"]:
-                    s_.wait_stream(cur)
-                for t in range(T):
-                    for k in range(K):
-                        with torch.cuda.stream(st["streams"][k]):
-                            sub_step(k, t)
-                for s_ in st["streams"]:
-                    cur.wait_stream(s_)
-            self._rctr += T
-            last_val = self.policy.predict_values(last)
-            finish(rb["rew"], rb["done_u8"], rb["val"], last_val, rb["adv"], rb["ret"])     # once over [T, N], after the streams joined
-            rb["done"].copy_(rb["done_u8"])     # the returned buffer's flags are fp32, as on the other paths; nothing here waits for it
-
-        with torch.no_grad():
-            if self.rollout_graph and K > 1:
-                if st["graph"] is None:
-                    side = torch.cuda.Stream(device=dev)        # warm-up off the default stream (real but uncounted env steps)
-                    side.wait_stream(torch.cuda.current_stream(dev))
-                    with torch.cuda.stream(side):
-                        fwd.pack()
-                        for k in range(K):
-                            sub_step(k, 0)
-                        self.policy.predict_values(last)
-                    torch.cuda.current_stream(dev).wait_stream(side)
-                    torch.cuda.synchronize(dev)
-                    st["graph"] = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(st["graph"], **(dict(capture_error_mode="thread_local") if dist.is_initialized() else {})):
-                        whole()
-                st["graph"].replay()
-            else:
-                whole()
-        self._last_obs = last
-        self.num_timesteps += T * N
-        self._rollout_stats()
-        return {k: v for k, v in rb.items() if k != "done_u8"}
-
-    def _rollout_graph_build(self):
-        """Capture the whole T-step rollout as ONE hipGraph with one chain per env sub-batch (own stream each): the
-        policy forward of one half overlaps the step kernel of the other, so the ramp-down of every launch is filled
-        (INTEGRATION.md "double-buffered halves"), and the ~35 launches per step cost no host time at replay."""
-        env, T, N, dev, bd = self.env, self.n_steps, self.n_envs, self.device, self.buffer_dtype
-        K = env.sub_batches
-        z = lambda *shape, dt=torch.float32: torch.zeros(*shape, device=dev, dtype=dt)
-        rb = dict(obs=z(T, N, self.obs_dim, dt=bd), act=z(T, N, self.act_dim, dt=bd), rew=z(T, N), done=z(T, N), val=z(T, N), logp=z(T, N),
-                  adv=z(T, N), ret=z(T, N))
-        last = env.reset_tensor().clone() if self._last_obs is None else self._last_obs.clone()
-        streams = concurrent_streams(dev, K)
-        finish = self._rollout_finish()
-
-        def chain(k, steps):
-            sl = env.sub_slices[k]
-            for t in range(steps):
-                obs = last[sl]
-                if self._fused_rollout_ok():
-                    sc, val = self._policy_step_fused(obs, env_index=k)
-                    out = env.step_sub(k, sc["act_env"])
-                    self._store_fused(rb, t, sl, last, sc, val, out, bump=True, env_index=k)
-                    continue
-                act, val, logp = self.policy(obs)
-                rb["obs"][t, sl] = obs
-                rb["act"][t, sl] = act
-                rb["val"][t, sl] = val
-                rb["logp"][t, sl] = logp
-                out = env.step_sub(k, torch.clamp(act, self.act_lo, self.act_hi))
-                rb["rew"][t, sl] = out["rew"]
-                rb["done"][t, sl] = out["done"].float()
-                last[sl].copy_(out["obs"])
-
-        with torch.no_grad():
-            # warm-up on the side streams (library workspaces, allocator pools); these env steps are real but uncounted
-            cur = torch.cuda.current_stream(dev)
-            for k in range(K):
-                streams[k].wait_stream(cur)
-                with torch.cuda.stream(streams[k]):
-                    chain(k, 1)
-            for k in range(K):
-                cur.wait_stream(streams[k])
-            torch.cuda.synchronize(dev)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, **(dict(capture_error_mode="thread_local") if dist.is_initialized() else {})):
-                cap = torch.cuda.current_stream(dev)
-                for k in range(K):
-                    streams[k].wait_stream(cap)
-                    with torch.cuda.stream(streams[k]):
-                        chain(k, T)
-                for k in range(K):
-                    cap.wait_stream(streams[k])
-                last_val = self.policy.predict_values(last)
-                finish(rb["rew"], rb["done"], rb["val"], last_val, rb["adv"], rb["ret"])      # one graph node chain, not ~6 T
-        self._rollout = (g, rb, last)
-
-    def _rollout_pipelined_eager(self):
-        """sub_batches > 1 without graph capture: the host issues step t of every sub-batch on that sub-batch's stream,
-        so the policy kernels of one overlap the step kernel of the other (14 launches per sub-batch step)."""
-        env, T, N, dev = self.env, self.n_steps, self.n_envs, self.device
-        K = env.sub_batches
-        if getattr(self, "_pipe", None) is None:
-            z = lambda *shape, dt=torch.float32: torch.zeros(*shape, device=dev, dtype=dt)
-            bd = self.buffer_dtype
-            rb = dict(obs=z(T, N, self.obs_dim, dt=bd), act=z(T, N, self.act_dim, dt=bd), rew=z(T, N), done=z(T, N), val=z(T, N), logp=z(T, N))
-            last = env.reset_tensor().clone() if self._last_obs is None else self._last_obs.clone()
-            self._pipe = (rb, last, concurrent_streams(dev, K))
-        rb, last, streams = self._pipe
-        cur = torch.cuda.current_stream(dev)
-        with torch.no_grad():
-            for st in streams:
-                st.wait_stream(cur)
-            for t in range(T):
-                for k in range(K):
-                    with torch.cuda.stream(streams[k]):
-                        sl = env.sub_slices[k]
-                        sc, val = self._policy_step_fused(last[sl], env_index=k)
-                        out = env.step_sub(k, sc["act_env"])
-                        self._store_fused(rb, t, sl, last, sc, val, out, bump=True, env_index=k)
-            for st in streams:
-                cur.wait_stream(st)
-            last_val = self.policy.predict_values(last)
-            rb["adv"], rb["ret"] = self._rollout_finish()(rb["rew"], rb["done"], rb["val"], last_val, rb.get("adv"), rb.get("ret"))
-        self._last_obs = last
-        self.num_timesteps += T * N
-        self._rollout_stats()
-        return rb
-
-    def _rollout_route(self):
-        """Which implementation collect_rollouts() runs: the one place that decides it."""
-        if self._fused_policy_ok():
-            return "policy_forward"
-        halves = getattr(self.env, "sub_batches", 1) > 1 and hasattr(self.env, "step_sub")
-        if not self.rollout_graph and self._fused_rollout_ok() and halves:
-            return "pipelined"
-        if self.rollout_graph and self.device.type == "cuda" and halves:
-            return "graph"
-        return "loop"
-
     def rollout_path(self):
         """Name of the rollout path this configuration takes, for run records: "policy_forward" (dm_policy_forward + dm_step per
         step, host-driven or captured), "sample_store" (library GEMMs + dm_policy_sample + dm_rollout_store, one stream or one per
-        sub-batch), "graph" (the captured rollout of _rollout_graph_build) or "plain" (PyTorch ops only)."""
-        route = self._rollout_route()
-        if route == "loop":
-            return "sample_store" if self._fused_rollout_ok() else "plain"
-        return "sample_store" if route == "pipelined" else route
+        sub-batch), "graph" (the captured sample_store / plain rollout) or "plain" (PyTorch ops only).  The first rollout
+        freezes the choice with its collector; from then on this reports what that collector runs."""
+        step, driver = route(self) if self._collector is None else (self._collector.step_kind, self._collector.driver)
+        return step if step == "policy_forward" or driver != "captured" else "graph"
 
     def collect_rollouts(self):
-        route = self._rollout_route()
-        if route == "policy_forward":
-            return self._rollout_fused_policy()
-        if route == "pipelined":
-            return self._rollout_pipelined_eager()
-        if route == "graph":
-            if getattr(self, "_rollout", None) is None:
-                self._rollout_graph_build()
-            g, rb, last = self._rollout
-            g.replay()
-            self._last_obs = last
-            self.num_timesteps += self.n_steps * self.n_envs
-            self._rollout_stats()
-            return rb
-        T, N, dev = self.n_steps, self.n_envs, self.device
-        bd = self.buffer_dtype
-        buf = dict(obs=torch.zeros(T, N, self.obs_dim, device=dev, dtype=bd), act=torch.zeros(T, N, self.act_dim, device=dev, dtype=bd),
-                   rew=torch.zeros(T, N, device=dev), done=torch.zeros(T, N, device=dev),
-                   val=torch.zeros(T, N, device=dev), logp=torch.zeros(T, N, device=dev))
-        if self._last_obs is None:
-            self._last_obs = self.env.reset_tensor().clone()
-        ep_done = 0
-        with torch.no_grad():
-            fused = self._fused_rollout_ok() and self._last_obs.is_contiguous()
-            full = slice(0, N)
-            for t in range(T):
-                obs = self._last_obs
-                if fused:
-                    sc, val = self._policy_step_fused(obs)
-                    out = self.env.step_tensor(sc["act_env"])
-                    self._store_fused(buf, t, full, self._last_obs, sc, val, out, bump=True)
-                    continue
-                act, val, logp = self.policy(obs)
-                out = self.env.step_tensor(torch.clamp(act, self.act_lo, self.act_hi))
-                buf["obs"][t] = obs
-                buf["act"][t] = act
-                buf["val"][t] = val
-                buf["logp"][t] = logp
-                buf["rew"][t] = out["rew"]
-                buf["done"][t] = out["done"].float()
-                self._last_obs = out["obs"].clone()
-            last_val = self.policy.predict_values(self._last_obs)
-            # GPU: dm_rollout_finish (bit for bit compute_gae); CPU: compute_gae itself and the same monitor in numpy
-            adv, ret = self._rollout_finish()(buf["rew"], buf["done"], buf["val"], last_val)
-        buf["adv"], buf["ret"] = adv, ret
-        self.num_timesteps += T * N
-        self._rollout_stats()
-        if dev.type != "cuda":                                   # the torch path keeps its fp32 means
-            self.stats["mean_reward"] = float(buf["rew"].mean())
-            self.stats["done_rate"] = float(buf["done"].mean())
-        return buf
+        return self.collector().collect()
 
     # ------------------------------------------------------------------ update
     def train(self, buf, generator=None):
@@ -1322,19 +850,12 @@ class PPO:
         return loss.detach()
 
     def _gather_minibatch(self, flat, idx, g):
-        import ctypes as C
-        from . import _lib
-        p = lambda t: C.c_void_p(t.data_ptr())
-        L = _lib.load_library()
         kind = gather_storage(flat, idx)
         if kind is None:
             raise ValueError("dm_ppo_gather takes fp32 or bf16 obs / act, fp32 adv / ret / logp and int64 indices")
-        rc = (L.dm_ppo_gather_bf16 if kind == "bf16" else L.dm_ppo_gather)(
-            p(idx), int(idx.numel()), p(flat["obs"]), self.obs_dim, p(flat["act"]), flat["act"].shape[1], p(flat["adv"]),
-            p(flat["ret"]), p(flat["logp"]), p(g["obs"]), p(g["act"]), p(g["adv"]), p(g["ret"]), p(g["logp"]),
-            C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
-        if rc != 0:
-            raise RuntimeError("dm_ppo_gather failed (%d)" % rc)
+        _lib.call("dm_ppo_gather_bf16" if kind == "bf16" else "dm_ppo_gather", idx, int(idx.numel()), flat["obs"], self.obs_dim, flat["act"],
+                  flat["act"].shape[1], flat["adv"], flat["ret"], flat["logp"], g["obs"], g["act"], g["adv"], g["ret"], g["logp"],
+                  device=self.device)
 
     def _capture_with_restore(self, warm, body):
         """Run ``warm`` three times on a side stream, capture ``body`` into a hipGraph, then put parameters and optimizer
@@ -1344,26 +865,11 @@ class PPO:
         snap_o = {k: {kk: (vv.clone() if torch.is_tensor(vv) else vv) for kk, vv in st.items()}
                   for k, st in self.optimizer.state.items()}
         had_state = len(self.optimizer.state) > 0
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):
-            for _ in range(3):
-                warm()
-        torch.cuda.current_stream(dev).wait_stream(side)
-        # with a process group alive, its watchdog thread queries events while we capture: "global" capture mode would
-        # fail the capture on that foreign call, "thread_local" only polices this thread
-        mode = dict(capture_error_mode="thread_local") if dist.is_initialized() else {}
-        if isinstance(body, (list, tuple)):      # several graphs captured back to back (e.g. around a collective)
-            graph, out = [], []
-            for b in body:
-                g_ = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g_, **mode):
-                    out.append(b())
-                graph.append(g_)
+        if isinstance(body, (list, tuple)):      # several graphs captured back to back (e.g. around a collective), warmed up once
+            got = [capture_graph(dev, b, warm=warm if i == 0 else None, warm_iters=3) for i, b in enumerate(body)]
+            graph, out = [g for g, _ in got], [o for _, o in got]
         else:
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph, **mode):
-                out = body()
+            graph, out = capture_graph(dev, body, warm=warm, warm_iters=3)
         with torch.no_grad():
             for p, q in zip(self.policy.parameters(), snap_p):
                 p.copy_(q)

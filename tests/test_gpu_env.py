@@ -579,8 +579,8 @@ def test_sub_batched_vecenv_and_captured_rollout(model):
     assert cont.any()
     buf2 = {k: v.clone() for k, v in buf.items()}
     ppo.collect_rollouts()                                                       # replay continues the same episodes
-    assert not torch.equal(buf2["obs"], ppo._rollout[1]["obs"])
-    ppo.train(ppo._rollout[1])
+    assert not torch.equal(buf2["obs"], ppo._collector.rb["obs"])
+    ppo.train(ppo._collector.rb)
     assert np.isfinite(ppo.stats["loss"])
     venv.close()
 
@@ -598,7 +598,7 @@ def test_fused_rollout_kernels(model):
     with torch.no_grad():
         ppo.policy.log_std.copy_(torch.linspace(-1.0, 0.5, 28))
         obs = venv.reset_tensor().clone()
-        sc, val = ppo._policy_step_fused(obs)
+        sc, val = ppo.collector().sample(obs)
         act1 = sc["act"].clone()
         mean = ppo.policy.action_net(ppo.policy.pi(obs))
         eps = (act1 - mean) / ppo.policy.log_std.exp()
@@ -608,7 +608,7 @@ def test_fused_rollout_kernels(model):
         assert torch.allclose(sc["logp"], ppo.policy._logp(act1, mean), atol=2e-4)
         assert torch.equal(sc["act_env"], torch.clamp(act1, ppo.act_lo, ppo.act_hi))
         assert torch.allclose(val, ppo.policy.predict_values(obs), atol=1e-6)
-        sc2, _ = ppo._policy_step_fused(obs)                                          # same counter -> same draw
+        sc2, _ = ppo.collector().sample(obs)                                           # same counter -> same draw
         assert torch.equal(sc2["act"], act1)
     buf = ppo.collect_rollouts()                                                       # counter advances once per step
     with torch.no_grad():
@@ -622,6 +622,21 @@ def test_fused_rollout_kernels(model):
         cont = buf["done"][0] == 0
         assert cont.float().mean() > 0.5 and torch.isfinite(buf["rew"]).all()
     venv.close()
+
+
+def test_failed_library_call_names_its_entry_point():
+    """`_lib.call` raises with the name of the entry point that was called and its return code: dm_rollout_store and
+    dm_rollout_store_bf16 refuse N = 0 on the host (-22) before they launch anything."""
+    import torch
+    from deepmimic_mujoco_amd import _lib
+    dev = torch.device("cuda", 0)
+    f = torch.zeros(8, device=dev)
+    u8 = torch.zeros(8, dtype=torch.uint8, device=dev)
+    for name in ("dm_rollout_store", "dm_rollout_store_bf16"):
+        with pytest.raises(RuntimeError, match=r"^%s failed \(-22\)$" % name):
+            _lib.call(name, 0, 2, 2, f, f, f, f, f, u8, f, f, f, f, f, f, f, f, None, device=dev)
+    torch.cuda.synchronize(dev)
+    assert float(f.abs().sum()) == 0.0 and int(u8.sum()) == 0      # nothing ran
 
 
 @pytest.mark.parametrize("arch,N,D", [((256, 128), 4096, 67), ((64, 32), 1000, 72), ((1024, 512), 2048, 67), ((96, 160), 33, 67)])

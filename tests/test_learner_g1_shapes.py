@@ -505,7 +505,7 @@ def test_g1_one_launch_policy_rollout(sub_batches, graph):
             m64, v64 = R.heads(P, buf["obs"][t])
             assert _note("rollout logp", float((buf["logp"][t].double() - R.logp(buf["act"][t], m64, P["log_std"])).abs().max()), 3e-4) < 3e-4
             assert _note("rollout value", float((buf["val"][t].double() - v64).abs().max()), 2e-5) < 2e-5
-        last_env = ppo._fp["act_env"]
+        last_env = ppo._collector.act_env
         assert torch.equal(last_env, torch.clamp(buf["act"][T - 1], lo, hi))
         assert bool(((last_env >= lo) & (last_env <= hi)).all()) and bool((last_env == hi).any() and (last_env == lo).any())
         o = twin.reset_tensor().clone()

@@ -225,9 +225,9 @@ def test_ppo_rollout_paths_use_the_kernel_and_match_the_references(path):
     for k in range(2):
         buf = ppo.collect_rollouts()
         if path.startswith("fused_policy"):
-            assert ppo._fp is not None and (ppo._fp["graph"] is not None) == cap
+            assert ppo._collector.step_kind == "policy_forward" and (ppo._collector.graph is not None) == cap
         else:
-            assert (getattr(ppo, "_rollout", None) is not None) == cap
+            assert (ppo._collector.graph is not None) == cap
         assert buf["done"].dtype == torch.float32
         with torch.no_grad():
             lv = ppo.policy.predict_values(ppo._last_obs)
