@@ -11,7 +11,7 @@ import os
 
 import numpy as np
 
-from .model import DmModel, NQ, NV, NU, NOBS
+from .model import DmModel, NBODY, NQ, NV, NU, NOBS
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libdeepmimic_hip.so")
@@ -200,8 +200,92 @@ def _ptr(t):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
-class HipEngine:
-    """Thin object wrapper over a DmHandle; all tensors are torch CUDA tensors owned by the caller."""
+class EngineBase:
+    """Handle lifetime and the entry points that ``dm_*`` (humanoid3d) and ``dmg1_*`` (Unitree G1) mirror.  A subclass sets
+    ``PREFIX``, the dimensions and, in its constructor, ``torch``, ``L``, ``h``, ``N``, ``device``, ``obs_dim``, ``terms_dim``,
+    ``_debug = None``; all tensors are torch CUDA tensors owned by the caller."""
+
+    PREFIX = None          # "dm_" / "dmg1_"
+    DEBUG_STRIDE = None    # floats per env of the debug buffer
+    NQ = NV = NBODY = None
+
+    def close(self):
+        if getattr(self, "h", None):
+            getattr(self.L, self.PREFIX + "destroy")(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _call(self, name, *args, stream=True):
+        """``<PREFIX><name>(handle, *args[, current stream])``: tensors go as their ``data_ptr()``; a non-zero return raises."""
+        entry = self.PREFIX + name
+        args = [_ptr(a) if isinstance(a, self.torch.Tensor) else a for a in args]
+        if stream:
+            args.append(C.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream))
+        rc = getattr(self.L, entry)(self.h, *args)
+        if rc != 0:
+            raise RuntimeError("%s failed (%d): %s" % (entry, rc, (getattr(self.L, self.PREFIX + "last_error")(self.h) or b"").decode()))
+
+    def _zeros(self, *shape, dtype=None):
+        return self.torch.zeros(self.N, *shape, dtype=dtype or self.torch.float32, device=self.device)
+
+    def alloc_outputs(self):
+        z, t = self._zeros, self.torch
+        return dict(obs=z(self.obs_dim), rew=z(), done=z(dtype=t.uint8), terms=z(self.terms_dim), reason=z(dtype=t.int32),
+                    terminal_obs=z(self.obs_dim))
+
+    def enable_debug(self, on=True):
+        self._debug = self._zeros(self.DEBUG_STRIDE) if on else None
+        self._call("set_debug", self._debug, stream=False)
+        return self._debug
+
+    def body_xpos(self, env=0):
+        """[nbody, 3] float64 world positions of ``env``'s bodies at its stored state.  The derived arrays are refreshed by a
+        forward evaluation and the warm start is put back: looking at an env is not physics."""
+        if self._debug is None:
+            self.enable_debug()
+        self._refresh_derived()
+        return self._debug[env, :3 * self.NBODY].double().cpu().numpy().reshape(self.NBODY, 3)
+
+    # ---- hot path
+    def reset(self, obs, idx_init=None, mask=None):
+        self._call("reset", mask, idx_init, obs)
+
+    def step(self, actions, out):
+        self._call("step", actions, out["obs"], out["rew"], out["done"], out.get("terms"), out.get("reason"), out.get("terminal_obs"))
+
+    def step_forced(self, qpos, qvel, out):
+        self._call("step_forced", qpos, qvel, out["obs"], out["rew"], out["done"], out.get("terms"), out.get("reason"))
+
+    def get_counters(self):
+        """(idx_curr int32[N], episode_length int32[N], episode_reward float32[N])"""
+        t = self.torch
+        idx, ln, rew = self._zeros(dtype=t.int32), self._zeros(dtype=t.int32), self._zeros()
+        self._call("get_counters", idx, ln, rew)
+        return idx, ln, rew
+
+    def set_counters(self, idx_curr=None, episode_length=None):
+        self._call("set_counters", idx_curr, episode_length)
+
+    def set_seed(self, seed):
+        """gym's env.seed(): re-key the reset / random-action generator."""
+        self._call("set_seed", int(seed) & 0xFFFFFFFFFFFFFFFF, stream=False)
+
+    def get_env_clips(self):
+        """Per-env clip id (DPEnv task) or motion id 0 walk / 1 run / 2 getup / 3 to_getup (combined task)."""
+        out = self._zeros(dtype=self.torch.int32)
+        self._call("get_env_clips", out)
+        return out
+
+
+class HipEngine(EngineBase):
+    """The humanoid3d engine: thin object wrapper over a DmHandle."""
+
+    PREFIX, DEBUG_STRIDE, NQ, NV, NBODY = "dm_", DEBUG_STRIDE, NQ, NV, NBODY
 
     def __init__(self, model, num_envs, device=0, seed=1234, auto_reset=True, integrator=None, **cfg_kw):
         import torch
@@ -225,133 +309,62 @@ class HipEngine:
         self.clip_len = {}
         self._debug = None
 
-    def set_seed(self, seed):
-        """gym's env.seed(): re-key the reset / random-action generator."""
-        self._chk(self.L.dm_set_seed(self.h, C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF)), "dm_set_seed")
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.dm_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _chk(self, rc, what):
-        if rc != 0:
-            msg = self.L.dm_last_error(self.h)
-            raise RuntimeError("%s failed (%d): %s" % (what, rc, msg.decode() if msg else ""))
-
-    def _stream(self):
-        return C.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
-
     # ---- clips
     def load_clip(self, clip_id, mocap, floor=False, acyclic=False):
         q, v, b, g = [np.ascontiguousarray(a, np.float64) for a in mocap.tables()]
-        self._chk(self.L.dm_load_clip(self.h, clip_id, len(q), q.ctypes.data_as(C.c_void_p),
-                                      v.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p),
-                                      g.ctypes.data_as(C.c_void_p)), "dm_load_clip")
+        self._call("load_clip", clip_id, len(q), *[a.ctypes.data_as(C.c_void_p) for a in (q, v, b, g)], stream=False)
         self.clip_len[clip_id] = len(q)
-        self._chk(self.L.dm_set_clip_flags(self.h, clip_id, (1 if floor else 0) | (2 if acyclic else 0)), "dm_set_clip_flags")
+        self._call("set_clip_flags", clip_id, (1 if floor else 0) | (2 if acyclic else 0), stream=False)
 
     def set_env_clips(self, clip_ids):
         t = None if clip_ids is None else clip_ids.to(self.device, self.torch.int32).contiguous()
-        self._chk(self.L.dm_set_env_clips(self.h, _ptr(t), self._stream()), "dm_set_env_clips")
+        self._call("set_env_clips", t)
         self._keep = t
 
-    def get_env_clips(self):
-        """Per-env clip id (DPEnv task) or motion id 0 walk / 1 run / 2 getup / 3 to_getup (combined task)."""
-        out = self.torch.zeros(self.N, dtype=self.torch.int32, device=self.device)
-        self._chk(self.L.dm_get_env_clips(self.h, _ptr(out), self._stream()), "dm_get_env_clips")
-        return out
-
-    # ---- buffers
-    def alloc_outputs(self):
-        t, d = self.torch, self.device
-        return dict(obs=t.zeros(self.N, self.obs_dim, device=d), rew=t.zeros(self.N, device=d),
-                    done=t.zeros(self.N, dtype=t.uint8, device=d), terms=t.zeros(self.N, self.terms_dim, device=d),
-                    reason=t.zeros(self.N, dtype=t.int32, device=d),
-                    terminal_obs=t.zeros(self.N, self.obs_dim, device=d))
-
-    def enable_debug(self, on=True):
-        if on:
-            self._debug = self.torch.zeros(self.N, DEBUG_STRIDE, device=self.device)
-            self._chk(self.L.dm_set_debug(self.h, _ptr(self._debug)), "dm_set_debug")
-        else:
-            self._chk(self.L.dm_set_debug(self.h, None), "dm_set_debug")
-            self._debug = None
-        return self._debug
-
-    # ---- hot path
-    def reset(self, obs, mask=None, idx_init=None):
-        self._chk(self.L.dm_reset(self.h, _ptr(mask), _ptr(idx_init), _ptr(obs), self._stream()), "dm_reset")
-
-    def step(self, actions, out):
-        self._chk(self.L.dm_step(self.h, _ptr(actions), _ptr(out["obs"]), _ptr(out["rew"]), _ptr(out["done"]),
-                                 _ptr(out.get("terms")), _ptr(out.get("reason")), _ptr(out.get("terminal_obs")),
-                                 self._stream()), "dm_step")
-
+    # ---- state
     def physics_step(self, actions):
         """sim.step() alone (src/deepmimic_env.py:362): the state advances, nothing is observed (dm_physics_step)."""
-        self._chk(self.L.dm_physics_step(self.h, _ptr(actions), self._stream()), "dm_physics_step")
-
-    def step_forced(self, qpos, qvel, out):
-        self._chk(self.L.dm_step_forced(self.h, _ptr(qpos), _ptr(qvel), _ptr(out["obs"]), _ptr(out["rew"]),
-                                        _ptr(out["done"]), _ptr(out.get("terms")), _ptr(out.get("reason")),
-                                        self._stream()), "dm_step_forced")
+        self._call("physics_step", actions)
 
     def set_state(self, qpos, qvel, warm=None, ctrl=None, env_ids=None, run_forward=False):
-        n = qpos.shape[0]
-        self._chk(self.L.dm_set_state(self.h, _ptr(env_ids), n, _ptr(qpos), _ptr(qvel), _ptr(warm), _ptr(ctrl),
-                                      1 if run_forward else 0, self._stream()), "dm_set_state")
+        self._call("set_state", env_ids, qpos.shape[0], qpos, qvel, warm, ctrl, 1 if run_forward else 0)
 
     def forward(self, env_ids=None, n=None):
         """sim.forward(): re-evaluate the derived quantities at the stored state."""
-        self._chk(self.L.dm_forward(self.h, _ptr(env_ids), self.N if n is None else n, self._stream()), "dm_forward")
+        self._call("forward", env_ids, self.N if n is None else n)
 
     def get_state(self, env_ids=None, n=None):
         t, d = self.torch, self.device
         n = self.N if n is None else n
         qpos, qvel = t.zeros(n, NQ, device=d), t.zeros(n, NV, device=d)
         warm, ctrl = t.zeros(n, NV, device=d), t.zeros(n, NU, device=d)
-        self._chk(self.L.dm_get_state(self.h, _ptr(env_ids), n, _ptr(qpos), _ptr(qvel), _ptr(warm), _ptr(ctrl),
-                                      self._stream()), "dm_get_state")
+        self._call("get_state", env_ids, n, qpos, qvel, warm, ctrl)
         return qpos, qvel, warm, ctrl
 
-    def get_counters(self):
-        t, d = self.torch, self.device
-        idx = t.zeros(self.N, dtype=t.int32, device=d)
-        ln = t.zeros(self.N, dtype=t.int32, device=d)
-        rew = t.zeros(self.N, device=d)
-        self._chk(self.L.dm_get_counters(self.h, _ptr(idx), _ptr(ln), _ptr(rew), self._stream()), "dm_get_counters")
-        return idx, ln, rew
-
-    def set_counters(self, idx=None, ep_len=None):
-        self._chk(self.L.dm_set_counters(self.h, _ptr(idx), _ptr(ep_len), self._stream()), "dm_set_counters")
+    def _refresh_derived(self):
+        q, v, w, c = self.get_state()
+        self.forward()
+        self.set_state(q, v, warm=w, ctrl=c, run_forward=False)     # the forward pass overwrote warm start and ctrl
 
     def fill_random_actions(self, actions, step_index):
-        self._chk(self.L.dm_fill_random_actions(self.h, _ptr(actions), int(step_index), self._stream()),
-                  "dm_fill_random_actions")
+        self._call("fill_random_actions", actions, int(step_index))
 
     def get_work(self):
-        w = self.torch.zeros(self.N, dtype=self.torch.int32, device=self.device)
-        self._chk(self.L.dm_get_work(self.h, _ptr(w), self._stream()), "dm_get_work")
+        w = self._zeros(dtype=self.torch.int32)
+        self._call("get_work", w)
         return w
 
     def enable_timing(self, on=True, stride=1):
         """HIP event pair around every ``stride``-th step-kernel launch (ring of 512 pairs, read by mean_step_ms)."""
-        self._chk(self.L.dm_enable_timing(self.h, max(1, int(stride)) if on else 0), "dm_enable_timing")
+        self._call("enable_timing", max(1, int(stride)) if on else 0, stream=False)
 
     def mean_step_ms(self):
         """(mean kernel ms, launches) over the steps since enable_timing(True); synchronises."""
         ms, n = C.c_float(0), C.c_int32(0)
-        self._chk(self.L.dm_mean_step_ms(self.h, C.byref(ms), C.byref(n)), "dm_mean_step_ms")
+        self._call("mean_step_ms", C.byref(ms), C.byref(n), stream=False)
         return ms.value, n.value
 
     def last_step_ms(self):
         ms = C.c_float(0)
-        self._chk(self.L.dm_last_step_ms(self.h, C.byref(ms)), "dm_last_step_ms")
+        self._call("last_step_ms", C.byref(ms), stream=False)
         return ms.value

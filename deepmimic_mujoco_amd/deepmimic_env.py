@@ -18,40 +18,8 @@ import numpy as np
 from . import _lib
 from .config import MotionConfig, RobotConfig
 from .mocap import MocapDM
-from .model import NOBS, NQ, NU, NV, load_model
-
-try:  # optional: real SB3 base class when present (it is not in this image)
-    from stable_baselines3.common.vec_env.base_vec_env import VecEnv as _SB3VecEnv
-except Exception:  # pragma: no cover
-    _SB3VecEnv = object
-
-
-class Box:
-    """Minimal stand-in for gym.spaces.Box (gym is not installed here)."""
-
-    def __init__(self, low, high, shape=None, dtype=np.float32):
-        self.dtype = np.dtype(dtype)
-        if shape is None:
-            shape = np.shape(low)
-        self.shape = tuple(shape)
-        self.low = np.broadcast_to(np.asarray(low, self.dtype), self.shape).copy()
-        self.high = np.broadcast_to(np.asarray(high, self.dtype), self.shape).copy()
-        self._rng = np.random.default_rng()
-
-    def sample(self):
-        lo = np.where(np.isfinite(self.low), self.low, -1.0)
-        hi = np.where(np.isfinite(self.high), self.high, 1.0)
-        return self._rng.uniform(lo, hi).astype(self.dtype)
-
-    def contains(self, x):
-        x = np.asarray(x)
-        return x.shape == self.shape and bool(np.all(x >= self.low) and np.all(x <= self.high))
-
-    def seed(self, seed=None):
-        self._rng = np.random.default_rng(seed)
-
-    def __repr__(self):
-        return "Box(%s, %s, %s, %s)" % (self.low.min(), self.high.max(), self.shape, self.dtype)
+from .model import NOBS, NU, NV, load_model
+from .vec_env import Box, HipBatchEnv, HipImitationEnv, LazyInfos, _INFO_KEYS, _action_space, _make_info  # noqa: F401 (re-exported)
 
 
 class DPEnvConfig:
@@ -69,20 +37,6 @@ class DPEnvConfig:
         self.ADD_PHASE_OBS = True
         self.ADD_PLAYER_ACTION_OBS = False
         self.MAX_PLAYER_ACTIONS = 3
-
-
-_INFO_KEYS = ["reward_config", "reward_qvel", "reward_end_eff", "reward_com", "reward_joint_limit"]
-
-
-def _make_info(terms, reason):
-    """info dict of deepmimic_env.py:251-255,424,438 (empty on the two early-out paths :378,:476)."""
-    if reason in (5, 6):
-        return {}
-    info = {k: float(v) for k, v in zip(_INFO_KEYS, terms)}
-    r = _lib.REASONS.get(int(reason))
-    if r is not None:
-        info["done_reason"] = r
-    return info
 
 
 class _SimView:
@@ -108,7 +62,7 @@ class _SimView:
         self._env._eng.forward()
 
 
-class DPEnv:
+class DPEnv(HipImitationEnv):
     """Single-clip imitation env with the reference's public surface (deepmimic_env.py:273)."""
 
     version = "v1.0"
@@ -147,9 +101,7 @@ class DPEnv:
         self.episode_reward = 0
         self.episode_length = 0
         self.sim = _SimView(self)
-        lo = self.model.act_ctrlrange[:, 0].astype(np.float32)
-        hi = self.model.act_ctrlrange[:, 1].astype(np.float32)
-        self.action_space = Box(lo, hi, dtype=np.float32)                     # from ctrlrange [EXT]
+        self.action_space = _action_space(self.model, NU)                     # from ctrlrange [EXT]
         self.observation_space = Box(-np.inf, np.inf, (NOBS,), np.float64)
         self.init_qpos = self.model.qpos0.copy()
         self.init_qvel = np.zeros(NV)
@@ -180,85 +132,19 @@ class DPEnv:
             self.idx_init = idx_init
         self.idx_curr = self.idx_init
 
-    def _push_counters(self):
-        t = self._torch
-        self._eng.set_counters(t.tensor([max(self.idx_curr, 0)], dtype=t.int32, device=self._eng.device),
-                               t.tensor([self.episode_length], dtype=t.int32, device=self._eng.device))
-
-    def _state(self):
-        q, v, _, _ = self._eng.get_state()
-        return q[0].double().cpu().numpy(), v[0].double().cpu().numpy()
-
     def _get_obs(self):
         raise NotImplementedError("observations are produced by dm_step/dm_reset; call step() or reset()")
 
     # ---- gym.Env surface ------------------------------------------------------------------
     def step(self, action, force_state=None):
-        t = self._torch
         action = np.asarray(action, np.float64) * 1.0
         assert action.shape == (NU,)                                          # deepmimic_env.py:352
-        self._push_counters()
-        if force_state is not None:
-            qpos, qvel = force_state
-            self._eng.step_forced(t.tensor(np.asarray(qpos)[None], dtype=t.float32, device=self._eng.device),
-                                  t.tensor(np.asarray(qvel)[None], dtype=t.float32, device=self._eng.device),
-                                  self._out)
-        else:
-            self._eng.step(t.tensor(action[None], dtype=t.float32, device=self._eng.device), self._out)
+        if force_state is None:
             self._time += self.model.timestep
-        obs = self._out["obs"][0].double().cpu().numpy()
-        reason = int(self._out["reason"][0].item())
-        done = bool(self._out["done"][0].item())
-        if self.mocap.data_config is None:                                    # deepmimic_env.py:394-395
-            return obs, 0, False, {}
-        if reason in (5, 6):                                                  # :366-378 / :465-476
-            if reason == 6:
-                # the reference advances idx_curr / episode_reward / episode_length (:452-455) BEFORE the observation
-                # guard (:465-476) zeroes the returned reward: take the pre-guard sum from the engine's counter
-                self.idx_curr = (self.idx_curr + 1) % self.mocap_data_len
-                self.episode_reward = float(self._eng.get_counters()[2][0].item())
-                self.episode_length += 1
-            return obs, 0, True, {}
-        reward = float(self._out["rew"][0].item())
-        info = _make_info(self._out["terms"][0].cpu().numpy(), reason)
-        self.idx_curr = (self.idx_curr + 1) % self.mocap_data_len              # :452-455
-        self.episode_reward += reward
-        self.episode_length += 1
-        return obs, reward, done, info
-
-    def reset(self):                                                          # :496-500
-        self.episode_reward = 0
-        self.episode_length = 0
-        return self.reset_model()
-
-    def reset_model(self, idx_init=None):                                     # :502-510
-        t = self._torch
-        self.reference_state_init(idx_init=idx_init)
-        obs = t.zeros(1, NOBS, device=self._eng.device)
-        self._eng.reset(obs, idx_init=t.tensor([self.idx_init], dtype=t.int32, device=self._eng.device))
-        self._eng.set_counters(None, t.tensor([self.episode_length], dtype=t.int32, device=self._eng.device))
-        return obs[0].double().cpu().numpy()
-
-    def set_state(self, qpos, qvel):                                          # MujocoEnv.set_state + sim.forward
-        t = self._torch
-        assert np.shape(qpos) == (NQ,) and np.shape(qvel) == (NV,)
-        self._eng.set_state(t.tensor(np.asarray(qpos)[None], dtype=t.float32, device=self._eng.device),
-                            t.tensor(np.asarray(qvel)[None], dtype=t.float32, device=self._eng.device),
-                            run_forward=True)
+        return self._imitation_step(action, force_state)
 
     def get_time(self):                                                       # :493
         return self._time
-
-    def render(self, mode=None):
-        """Software stick figure (render.py) of the current body poses: there is no MuJoCo viewer behind this env."""
-        from .render import stick_figure
-        if self._eng._debug is None:
-            self._eng.enable_debug()
-        q, v, w, c = self._eng.get_state()
-        self._eng.forward()                                     # refresh the derived arrays of the stored state ...
-        self._eng.set_state(q, v, warm=w, ctrl=c, run_forward=False)   # ... and put the warm start back: rendering is not physics
-        xpos = self._eng._debug[0, :42].double().cpu().numpy().reshape(14, 3)
-        return stick_figure(xpos, self.model.body_parent)
 
     def seed(self, seed=None):
         random.seed(seed)
@@ -266,91 +152,15 @@ class DPEnv:
             self._eng.set_seed(seed)
         return [seed]
 
-    def close(self):
-        self._eng.close()
 
-
-class LazyInfos(list):
-    """`infos` of a VecEnv step: a real ``list`` (SB3's wrappers slice it, assign into it and test it with
-    ``isinstance(infos, (list, tuple))``) whose dicts are built on first access — 4096 dicts per step would dominate the
-    numpy surface.  Unmaterialised slots hold ``None`` internally; every public access path materialises them."""
-
-    _make = staticmethod(lambda terms, reason: _make_info(terms, reason))
-
-    def __init__(self, terms, reason, done, terminal_obs):
-        super().__init__([None] * len(done))
-        self._terms, self._reason, self._done, self._tobs = terms, reason, done, terminal_obs
-
-    def _get(self, i):
-        v = list.__getitem__(self, i)
-        if v is None:
-            if i < 0:
-                i += len(self)
-            v = self._make(self._terms[i], self._reason[i])
-            if self._done[i]:
-                v["terminal_observation"] = self._tobs[i].copy()
-            list.__setitem__(self, i, v)
-        return v
-
-    def __getitem__(self, i):
-        if isinstance(i, slice):
-            return [self._get(j) for j in range(*i.indices(len(self)))]
-        return self._get(i)
-
-    def __iter__(self):
-        return (self._get(i) for i in range(len(self)))
-
-    def _all(self):
-        return [self._get(i) for i in range(len(self))]
-
-    def copy(self):
-        return self._all()
-
-    def __eq__(self, other):
-        return self._all() == list(other)
-
-    __hash__ = None
-
-    # every list operation that would read the raw (unmaterialised) slots goes through _all()
-    def __add__(self, other):
-        return self._all() + list(other)
-
-    def __radd__(self, other):
-        return list(other) + self._all()
-
-    def __mul__(self, k):
-        return self._all() * k
-
-    __rmul__ = __mul__
-
-    def __reversed__(self):
-        return reversed(self._all())
-
-    def __contains__(self, item):
-        return item in self._all()
-
-    def count(self, item):
-        return self._all().count(item)
-
-    def index(self, item, *a):
-        return self._all().index(item, *a)
-
-    def __repr__(self):
-        return repr(self._all())
-
-    def __reduce__(self):          # pickles / deep-copies as the plain list it stands for
-        return (list, (self._all(),))
-
-    def __repr__(self):
-        return repr(self._all())
-
-
-class HipDeepMimicVecEnv(_SB3VecEnv):
+class HipDeepMimicVecEnv(HipBatchEnv):
     """N DPEnv instances as one HIP batch with SubprocVecEnv semantics (auto-reset, terminal_observation).
 
     ``motion`` may be one clip name or a list (per-env clip id = env index mod len(list): BASELINE
     config 5).  ``step_tensor`` is the zero-copy path used by deepmimic_mujoco_amd.ppo.
     """
+
+    version, ENV_CFG = DPEnv.version, DPEnv.ENV_CFG
 
     def __new__(cls, num_envs, motion=None, robot="humanoid3d", device=0, seed=1234, auto_reset=True, sub_batches=1):
         if robot == "unitree_g1" and cls is HipDeepMimicVecEnv:
@@ -360,154 +170,23 @@ class HipDeepMimicVecEnv(_SB3VecEnv):
 
     def __init__(self, num_envs, motion=None, robot="humanoid3d", device=0, seed=1234, auto_reset=True, sub_batches=1):
         import torch
-        self._torch = torch
         self.robot_config = RobotConfig(robot)
-        self.model = load_model(self.robot_config.xml_path)
-        self.num_envs = int(num_envs)
-        self.sub_batches = int(sub_batches)
-        assert self.sub_batches >= 1 and self.num_envs % self.sub_batches == 0
-        nk = self.num_envs // self.sub_batches
+        model = load_model(self.robot_config.xml_path)
         motions = [motion] if (motion is None or isinstance(motion, str)) else list(motion)
         self.motions = [MotionConfig(m, robot).motion for m in motions]
-        # sub_batches > 1: independent engines over contiguous env ranges, so a rollout can keep one range simulating
-        # while the policy runs on another (deepmimic_mujoco_amd.ppo; INTEGRATION.md "double-buffered halves")
-        self.engines = [_lib.HipEngine(self.model, nk, device=device, seed=seed + 104729 * k, auto_reset=auto_reset,
-                                       low_z=self.robot_config.low_z) for k in range(self.sub_batches)]
-        self.engine = self.engines[0]
         self.mocaps = []
-        for cid, m in enumerate(self.motions):
-            mc = MocapDM(robot=robot, model=self.model)
+        for m in self.motions:
+            mc = MocapDM(robot=robot, model=model)
             mc.load_mocap(MotionConfig(m, robot).mocap_path)
-            mcfg = MotionConfig(m, robot)
-            for e in self.engines:
-                e.load_clip(cid, mc, floor=m in mcfg.floor_motions, acyclic=m in mcfg.acyclical_motions)
             self.mocaps.append(mc)
-        if len(self.motions) > 1:
-            for k, e in enumerate(self.engines):
+
+        def make(nk, k):
+            e = _lib.HipEngine(model, nk, device=device, seed=seed + 104729 * k, auto_reset=auto_reset, low_z=self.robot_config.low_z)
+            for cid, (m, mc) in enumerate(zip(self.motions, self.mocaps)):
+                mcfg = MotionConfig(m, robot)
+                e.load_clip(cid, mc, floor=m in mcfg.floor_motions, acyclic=m in mcfg.acyclical_motions)
+            if len(self.motions) > 1:
                 ids = (torch.arange(nk, device=e.device) + k * nk) % len(self.motions)
                 e.set_env_clips(ids.to(torch.int32))
-        self.device = self.engine.device
-        if self.sub_batches == 1:
-            self.out = self.engine.alloc_outputs()
-            self.sub_out = [self.out]
-        else:   # one set of [N, ...] tensors; every engine writes its contiguous block of rows
-            z = lambda *shape, dt=torch.float32: torch.zeros(*shape, device=self.device, dtype=dt)
-            N = self.num_envs
-            self.out = dict(obs=z(N, NOBS), rew=z(N), done=z(N, dt=torch.uint8), terms=z(N, 5), reason=z(N, dt=torch.int32),
-                            terminal_obs=z(N, NOBS))
-            self.sub_out = [{k_: v[k * nk:(k + 1) * nk] for k_, v in self.out.items()} for k in range(self.sub_batches)]
-        self.sub_slices = [slice(k * nk, (k + 1) * nk) for k in range(self.sub_batches)]
-        lo = self.model.act_ctrlrange[:, 0].astype(np.float32)
-        hi = self.model.act_ctrlrange[:, 1].astype(np.float32)
-        self.action_space = Box(lo, hi, dtype=np.float32)
-        self.observation_space = Box(-np.inf, np.inf, (NOBS,), np.float32)
-        self._actions = torch.zeros(self.num_envs, NU, device=self.device)
-        self.version, self.ENV_CFG = DPEnv.version, DPEnv.ENV_CFG
-        self.render_mode = None
-        self.reset_infos = [{} for _ in range(self.num_envs)]
-        if _SB3VecEnv is not object:  # pragma: no cover
-            _SB3VecEnv.__init__(self, self.num_envs, self.observation_space, self.action_space)
-
-    # ---- zero-copy tensor API
-    def reset_tensor(self, idx_init=None):
-        for e, o, sl in zip(self.engines, self.sub_out, self.sub_slices):
-            e.reset(o["obs"], idx_init=None if idx_init is None else idx_init[sl].contiguous())
-        return self.out["obs"]
-
-    def step_tensor(self, actions):
-        """actions: float32 CUDA tensor [N,28] -> dict of CUDA tensors (obs, rew, done, terms, reason, terminal_obs)."""
-        actions = actions.contiguous()
-        for e, o, sl in zip(self.engines, self.sub_out, self.sub_slices):
-            e.step(actions[sl], o)
-        return self.out
-
-    def step_sub(self, k, actions_k):
-        """Step sub-batch k only (on the current stream): actions_k [N/sub_batches, 28] -> its slice of the outputs."""
-        self.engines[k].step(actions_k.contiguous(), self.sub_out[k])
-        return self.sub_out[k]
-
-    # ---- SB3 VecEnv protocol (numpy in / numpy out)
-    def reset(self):
-        return self.reset_tensor().cpu().numpy()
-
-    def step_async(self, actions):
-        t = self._torch
-        self._actions.copy_(t.as_tensor(np.ascontiguousarray(actions, dtype=np.float32)).reshape(self._actions.shape))
-
-    def step_wait(self):
-        """numpy surface: the six outputs are packed into one [N, 2 obs + terms + 3] float32 device tensor (one small
-        kernel) and cross PCIe as ONE download + synchronisation (2.3 MB at 4 096 envs); CPU reads of ROCm's pinned
-        staging memory are uncached, so the download targets ordinary pageable memory."""
-        t = self._torch
-        out = self.step_tensor(self._actions)
-        packed = t.cat([out["obs"], out["terminal_obs"], out["terms"], out["rew"][:, None], out["done"][:, None].float(),
-                        out["reason"][:, None].float()], dim=1).cpu().numpy()
-        d, k = out["obs"].shape[1], out["terms"].shape[1]
-        obs, tobs, terms = (np.ascontiguousarray(packed[:, 0:d]), np.ascontiguousarray(packed[:, d:2 * d]),
-                            np.ascontiguousarray(packed[:, 2 * d:2 * d + k]))
-        rew = packed[:, 2 * d + k].copy()
-        done = packed[:, 2 * d + k + 1] != 0
-        reason = packed[:, 2 * d + k + 2].astype(np.int32)
-        return obs, rew, done, LazyInfos(terms, reason, done, tobs)
-
-    def step(self, actions):
-        self.step_async(actions)
-        return self.step_wait()
-
-    def close(self):
-        for e in getattr(self, "engines", [self.engine]):
-            e.close()
-
-    def seed(self, seed=None):
-        """SB3 VecEnv.seed: env i gets seed + i.  Here: re-keys the engines' counter-based reset generator (env index and
-        reset count are part of the key already) and returns the per-env seeds SB3 expects."""
-        if seed is None:
-            return [None] * self.num_envs
-        for k, e in enumerate(self.engines):
-            e.set_seed(int(seed) + 104729 * k)
-        return [int(seed) + i for i in range(self.num_envs)]
-
-    def _n_indices(self, indices):
-        return self.num_envs if indices is None else len(np.atleast_1d(indices))
-
-    def get_attr(self, attr_name, indices=None):
-        return [getattr(self, attr_name)] * self._n_indices(indices)
-
-    def set_attr(self, attr_name, value, indices=None):
-        setattr(self, attr_name, value)
-
-    def env_method(self, method_name, *args, indices=None, **kwargs):
-        """SB3 VecEnv.env_method: the envs of the batch are identical, so a method of the batch object answers for every
-        env (what SB3 itself uses it for: ``seed``, ``get_wrapper_attr``-style queries); unknown names raise
-        AttributeError as a missing method of a sub-env would."""
-        fn = getattr(self, method_name)
-        out = fn(*args, **kwargs)
-        return [out] * self._n_indices(indices)
-
-    def getattr_depth_check(self, name, already_found):
-        return None
-
-    @property
-    def unwrapped(self):
-        return self
-
-    def env_is_wrapped(self, wrapper_class, indices=None):
-        n = self.num_envs if indices is None else len(np.atleast_1d(indices))
-        return [False] * n
-
-    def get_images(self):
-        """One frame per env in SB3; a 4 096-tile mosaic is of no use: the frame of env 0 stands for the batch."""
-        return [self.render(mode="rgb_array")]
-
-    def render(self, mode=None):
-        """Software stick figure (render.py) of env 0 of the batch, 240 x 320 x 3 uint8 (what VecVideoRecorder-style callers get).
-        The derived arrays are refreshed by a forward evaluation and the warm start is put back: rendering is not physics."""
-        from .render import stick_figure
-        e = self.engine
-        if e._debug is None:
-            e.enable_debug()
-        q, v, w, c = e.get_state()
-        e.forward()
-        e.set_state(q, v, warm=w, ctrl=c, run_forward=False)
-        xpos = e._debug[0, :42].double().cpu().numpy().reshape(14, 3)
-        return stick_figure(xpos, self.model.body_parent)
+            return e
+        super().__init__(num_envs, sub_batches, make, model, NOBS, 5, NU)

@@ -13,6 +13,8 @@ import os
 import numpy as np
 
 from . import mjcf, model as _model
+from ._lib import EngineBase, load_library
+from .vec_env import Box, HipBatchEnv, HipImitationEnv, HipSingleEnv, _LazyCombinedInfos, _action_space, _combined_info
 from .config import RobotConfig
 
 NQ, NV, NU, NBODY, NGEOM, NJNT, NM, MAXPAIR, NOBS = 44, 43, 37, 39, 94, 38, 434, 1024, 85
@@ -144,7 +146,6 @@ _BOUND = []
 
 
 def _lib():
-    from ._lib import load_library
     L = load_library()
     if not _BOUND:
         vp, i32 = C.c_void_p, C.c_int
@@ -178,12 +179,10 @@ def _lib():
     return L
 
 
-def _ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-class G1HipEngine:
+class G1HipEngine(EngineBase):
     """Batch of N Unitree G1 DeepMimic environments resident on one MI355X (tensors in, tensors out)."""
+
+    PREFIX, DEBUG_STRIDE, NQ, NV, NBODY = "dmg1_", DEBUG_STRIDE, NQ, NV, NBODY
 
     def __init__(self, num_envs, device=0, seed=0, auto_reset=True, max_ep_length=1000, task=TASK_DPENV, pipeline=0):
         import torch
@@ -210,98 +209,50 @@ class G1HipEngine:
         self.clip_len = 0
         self._debug = None
 
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.dmg1_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _check(self, rc, what):
-        if rc != 0:
-            raise RuntimeError("%s failed (%d): %s" % (what, rc, (self.L.dmg1_last_error(self.h) or b"").decode()))
-
-    def _stream(self):
-        return C.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
-
     def load_clip(self, mocap, floor=False, acyclic=False, run_rule=False, clip_id=0):
         q, v, bx, gx = [np.ascontiguousarray(a, np.float64) for a in mocap.tables()]
         if clip_id == 0:
             self.clip_len = len(q)
         flags = (CLIP_FLOOR if floor else 0) | (CLIP_ACYCLIC if acyclic else 0) | (CLIP_RUN_RULE if run_rule else 0)
-        self._check(self.L.dmg1_load_clip(self.h, int(clip_id), len(q), q.ctypes.data, v.ctypes.data, bx.ctypes.data, gx.ctypes.data,
-                                          flags), "dmg1_load_clip")
+        self._call("load_clip", int(clip_id), len(q), q.ctypes.data, v.ctypes.data, bx.ctypes.data, gx.ctypes.data, flags, stream=False)
 
-    def alloc_outputs(self):
-        t, d, n = self.torch, self.device, self.N
-        return dict(obs=t.zeros(n, self.obs_dim, device=d), rew=t.zeros(n, device=d), done=t.zeros(n, dtype=t.uint8, device=d),
-                    terms=t.zeros(n, self.terms_dim, device=d), reason=t.zeros(n, dtype=t.int32, device=d),
-                    terminal_obs=t.zeros(n, self.obs_dim, device=d))
-
-    def reset(self, obs, idx_init=None, mask=None):
-        self._check(self.L.dmg1_reset(self.h, _ptr(mask), _ptr(idx_init), _ptr(obs), self._stream()), "dmg1_reset")
+    def _rows(self, qpos, qvel):
+        return qpos.shape == (self.N, NQ) and qvel.shape == (self.N, NV) and qpos.is_contiguous() and qvel.is_contiguous()
 
     def step(self, actions, out):
         assert actions.shape == (self.N, NACT) and actions.dtype == self.torch.float32 and actions.is_contiguous()
-        self._check(self.L.dmg1_step(self.h, _ptr(actions), _ptr(out["obs"]), _ptr(out["rew"]), _ptr(out["done"]),
-                                     _ptr(out.get("terms")), _ptr(out.get("reason")), _ptr(out.get("terminal_obs")), self._stream()),
-                    "dmg1_step")
+        super().step(actions, out)
 
     def step_forced(self, qpos, qvel, out):
-        assert qpos.shape == (self.N, NQ) and qvel.shape == (self.N, NV) and qpos.is_contiguous() and qvel.is_contiguous()
-        self._check(self.L.dmg1_step_forced(self.h, _ptr(qpos), _ptr(qvel), _ptr(out["obs"]), _ptr(out["rew"]), _ptr(out["done"]),
-                                            _ptr(out["terms"]), _ptr(out["reason"]), self._stream()), "dmg1_step_forced")
+        assert self._rows(qpos, qvel)
+        super().step_forced(qpos, qvel, out)
 
     def set_state(self, qpos, qvel, warm=None, run_forward=True):
-        assert qpos.shape == (self.N, NQ) and qvel.shape == (self.N, NV) and qpos.is_contiguous() and qvel.is_contiguous()
-        self._check(self.L.dmg1_set_state(self.h, _ptr(qpos), _ptr(qvel), _ptr(warm), int(run_forward), self._stream()),
-                    "dmg1_set_state")
+        assert self._rows(qpos, qvel)
+        self._call("set_state", qpos, qvel, warm, int(run_forward))
 
     def get_state(self):
-        t, d, n = self.torch, self.device, self.N
-        q, v, w = t.zeros(n, NQ, device=d), t.zeros(n, NV, device=d), t.zeros(n, NV, device=d)
-        self._check(self.L.dmg1_get_state(self.h, _ptr(q), _ptr(v), _ptr(w), self._stream()), "dmg1_get_state")
+        q, v, w = self._zeros(NQ), self._zeros(NV), self._zeros(NV)
+        self._call("get_state", q, v, w)
         return q, v, w
 
-    def get_counters(self):
-        t, d, n = self.torch, self.device, self.N
-        i, l, r = t.zeros(n, dtype=t.int32, device=d), t.zeros(n, dtype=t.int32, device=d), t.zeros(n, device=d)
-        self._check(self.L.dmg1_get_counters(self.h, _ptr(i), _ptr(l), _ptr(r), self._stream()), "dmg1_get_counters")
-        return i, l, r
-
-    def set_counters(self, idx_curr=None, episode_length=None):
-        self._check(self.L.dmg1_set_counters(self.h, _ptr(idx_curr), _ptr(episode_length), self._stream()), "dmg1_set_counters")
+    def _refresh_derived(self):
+        q, v, w = self.get_state()
+        self.set_state(q, v, warm=w, run_forward=True)
+        self.set_state(q, v, warm=w, run_forward=False)     # the forward pass overwrote the warm start
 
     def get_motion(self):
-        m = self.torch.zeros(self.N, dtype=self.torch.int32, device=self.device)
-        self._check(self.L.dmg1_get_motion(self.h, _ptr(m), self._stream()), "dmg1_get_motion")
+        m = self._zeros(dtype=self.torch.int32)
+        self._call("get_motion", m)
         return m
 
     def set_motion(self, motion):
-        self._check(self.L.dmg1_set_motion(self.h, _ptr(motion), self._stream()), "dmg1_set_motion")
-
-    def set_seed(self, seed):
-        """gym.Env.seed(): re-keys the RSI reset generator (dmg1_set_seed)."""
-        self._check(self.L.dmg1_set_seed(self.h, int(seed) & 0xFFFFFFFFFFFFFFFF), "dmg1_set_seed")
+        self._call("set_motion", motion)
 
     def set_env_clips(self, clip_ids):
         """DPEnv task: per-env clip id (int32 device tensor [N]) among the loaded clip slots."""
         assert clip_ids.dtype == self.torch.int32 and clip_ids.numel() == self.N and clip_ids.is_contiguous()
-        self._check(self.L.dmg1_set_env_clips(self.h, _ptr(clip_ids), self._stream()), "dmg1_set_env_clips")
-
-    def get_env_clips(self):
-        m = self.torch.zeros(self.N, dtype=self.torch.int32, device=self.device)
-        self._check(self.L.dmg1_get_env_clips(self.h, _ptr(m), self._stream()), "dmg1_get_env_clips")
-        return m
-
-    def enable_debug(self):
-        self._debug = self.torch.zeros(self.N, DEBUG_STRIDE, device=self.device)
-        self.L.dmg1_set_debug(self.h, _ptr(self._debug))
-        return self._debug
+        self._call("set_env_clips", clip_ids)
 
     def last_kernel_ms(self):
         return float(self.L.dmg1_last_kernel_ms(self.h))
@@ -310,17 +261,11 @@ class G1HipEngine:
         """split pipeline: per round of the last step (support-query pair tickets, analytic pair tickets, tickets pulled)."""
         buf = (C.c_int32 * 24)()
         self.L.dmg1_queue_counters.argtypes = [C.c_void_p, C.c_void_p]
-        self._check(self.L.dmg1_queue_counters(self.h, buf), "dmg1_queue_counters")
+        self._call("queue_counters", buf, stream=False)
         return [tuple(buf[4 * r:4 * r + 3]) for r in range(6)]
 
 
 # ------------------------------------------------------------------------------------------ Gym / VecEnv surfaces
-try:  # pragma: no cover - SB3 is not installed in the build image; with it the batch classes ARE VecEnvs (isinstance checks of wrappers)
-    from stable_baselines3.common.vec_env.base_vec_env import VecEnv as _SB3VecEnv
-except Exception:  # noqa: BLE001
-    _SB3VecEnv = object
-
-
 def _g1_mocap(motion):
     from .config import MotionConfig
     from .mocap import MocapDM
@@ -330,19 +275,16 @@ def _g1_mocap(motion):
     return mcfg, mc
 
 
-def _load(engine, mcfg, mc):
+def _load(engine, mcfg, mc, clip_id=0):
     engine.load_clip(mc, floor=mcfg.motion in mcfg.floor_motions, acyclic=mcfg.motion in mcfg.acyclical_motions,
-                     run_rule=mcfg.motion == "run")                                  # src/deepmimic_env.py:426
+                     run_rule=mcfg.motion == "run", clip_id=clip_id)                 # src/deepmimic_env.py:426
 
 
-class HipG1VecEnv(_SB3VecEnv):
+class HipG1VecEnv(HipBatchEnv):
     """N ``DPEnv(robot="unitree_g1")`` instances as one HIP batch with SubprocVecEnv semantics (auto-reset,
     ``terminal_observation``): the G1 counterpart of :class:`deepmimic_env.HipDeepMimicVecEnv`, which constructs this class
     when asked for ``robot="unitree_g1"``.  Actions are the policy's 23 values (src/deepmimic_env.py:303-307).
-    ``motion`` may be a list (per-env clip id = env index mod len(list), as BASELINE config 5 mixes clips); ``sub_batches`` > 1
-    splits the batch into independent engines over contiguous env ranges (double-buffered rollouts, see HipDeepMimicVecEnv)."""
-
-    OBS_DIM, TERMS_DIM = NOBS, 5
+    ``motion`` may be a list (per-env clip id = env index mod len(list), as BASELINE config 5 mixes clips)."""
 
     def __init__(self, num_envs, motion=None, device=0, seed=1234, auto_reset=True, sub_batches=1):
         from .deepmimic_env import DPEnvConfig
@@ -352,68 +294,23 @@ class HipG1VecEnv(_SB3VecEnv):
         self.motion_config, self.mocap = pairs[0]
         self.motions = [mcfg.motion for mcfg, _ in pairs]
         self.mocaps = [mc for _, mc in pairs]
+        self.robot_config = RobotConfig("unitree_g1")
 
         def make(nk, k):
             e = G1HipEngine(nk, device=device, seed=seed + 104729 * k, auto_reset=auto_reset, max_ep_length=DPEnvConfig().MAX_EP_LENGTH)
             for cid, (mcfg, mc) in enumerate(pairs):
-                e.load_clip(mc, floor=mcfg.motion in mcfg.floor_motions, acyclic=mcfg.motion in mcfg.acyclical_motions,
-                            run_rule=mcfg.motion == "run", clip_id=cid)                 # src/deepmimic_env.py:426
+                _load(e, mcfg, mc, clip_id=cid)
             if len(pairs) > 1:
                 ids = (e.torch.arange(nk, device=e.device) + k * nk) % len(pairs)
                 e.set_env_clips(ids.to(e.torch.int32).contiguous())
             return e
-        self._build(num_envs, sub_batches, make, scale=1.0)
+        super().__init__(num_envs, sub_batches, make, load_g1_model()[0], NOBS, 5, NACT)
 
-    def _build(self, num_envs, sub_batches, make_engine, scale):
-        """Common construction: engines over contiguous env ranges, one set of [N, ...] output tensors, spaces."""
-        import torch
-        from .deepmimic_env import Box
-        self._torch = torch
-        self.num_envs, self.sub_batches = int(num_envs), int(sub_batches)
-        assert self.sub_batches >= 1 and self.num_envs % self.sub_batches == 0
-        nk = self.num_envs // self.sub_batches
-        self.robot_config = RobotConfig("unitree_g1")
-        self.engines = [make_engine(nk, k) for k in range(self.sub_batches)]
-        self.engine = self.engines[0]
-        self.model = self.engine.gmodel
-        self.device = self.engine.device
-        if self.sub_batches == 1:
-            self.out = self.engine.alloc_outputs()
-        else:   # every engine writes its contiguous block of rows
-            z = lambda *shape, dt=torch.float32: torch.zeros(*shape, device=self.device, dtype=dt)
-            N, D, K = self.num_envs, self.OBS_DIM, self.TERMS_DIM
-            self.out = dict(obs=z(N, D), rew=z(N), done=z(N, dt=torch.uint8), terms=z(N, K), reason=z(N, dt=torch.int32), terminal_obs=z(N, D))
-        self.sub_slices = [slice(k * nk, (k + 1) * nk) for k in range(self.sub_batches)]
-        self.sub_out = [self.out] if self.sub_batches == 1 else [{k_: v[sl] for k_, v in self.out.items()} for sl in self.sub_slices]
-        lo = self.model.act_ctrlrange[:NACT, 0].astype(np.float32) * scale
-        hi = self.model.act_ctrlrange[:NACT, 1].astype(np.float32) * scale
-        self.action_space = Box(lo, hi, dtype=np.float32)            # the first N - 14 actuators (src/deepmimic_env.py:305-307)
-        self.observation_space = Box(-np.inf, np.inf, (self.OBS_DIM,), np.float32)
-        self._actions = torch.zeros(self.num_envs, NACT, device=self.device)
-        self.render_mode = None
-        self.reset_infos = [{} for _ in range(self.num_envs)]
-        if _SB3VecEnv is not object:  # pragma: no cover
-            _SB3VecEnv.__init__(self, self.num_envs, self.observation_space, self.action_space)
-
-    def step_sub(self, k, actions_k):
-        """Step sub-batch k only (on the current stream): actions_k [N / sub_batches, 23] -> its slice of the outputs."""
-        self.engines[k].step(actions_k.contiguous(), self.sub_out[k])
-        return self.sub_out[k]
-
-    def reset_tensor(self, idx_init=None):
-        for e, o, sl in zip(self.engines, self.sub_out, self.sub_slices):
-            e.reset(o["obs"], idx_init=None if idx_init is None else idx_init[sl].contiguous())
-        return self.out["obs"]
-
-    def step_tensor(self, actions):
-        """One step of the whole batch.  With sub_batches > 1 every engine's launches go to its own HIP stream, forked from and
-        joined back into the current one: while one engine's g1_env_kernel drains its heaviest envs, the CUs it has left idle
-        run the other engines' kernels (the envs of a batch are independent; results do not depend on the overlap)."""
+    def _step_engines(self, actions):
+        """sub_batches > 1: every engine's launches go to its own HIP stream, forked from and joined back into the current one.
+        While one engine's g1_env_kernel drains its heaviest envs, the CUs it has left idle run the other engines' kernels (the
+        envs of a batch are independent; results do not depend on the overlap).  The humanoid step has no such tail."""
         t = self._torch
-        actions = actions.contiguous()
-        if self.sub_batches == 1:
-            self.engine.step(actions, self.out)
-            return self.out
         cur = t.cuda.current_stream(self.device)
         if getattr(self, "_streams", None) is None:
             from .streams import concurrent_streams
@@ -424,100 +321,19 @@ class HipG1VecEnv(_SB3VecEnv):
             with t.cuda.stream(s):
                 e.step(actions[sl], o)
             cur.wait_event(s.record_event())
-        return self.out
-
-    def reset(self):
-        return self.reset_tensor().cpu().numpy()
-
-    def step_async(self, actions):
-        t = self._torch
-        self._actions.copy_(t.as_tensor(np.ascontiguousarray(actions, dtype=np.float32)).reshape(self._actions.shape))
-
-    def _infos(self, terms, reason, done, tobs):
-        from .deepmimic_env import LazyInfos
-        return LazyInfos(terms, reason, done, tobs)
-
-    def step_wait(self):
-        t = self._torch
-        out = self.step_tensor(self._actions)
-        packed = t.cat([out["obs"], out["terminal_obs"], out["terms"], out["rew"][:, None], out["done"][:, None].float(),
-                        out["reason"][:, None].float()], dim=1).cpu().numpy()
-        d, k = self.OBS_DIM, self.TERMS_DIM
-        obs, tobs, terms = (np.ascontiguousarray(packed[:, 0:d]), np.ascontiguousarray(packed[:, d:2 * d]),
-                            np.ascontiguousarray(packed[:, 2 * d:2 * d + k]))
-        rew = packed[:, 2 * d + k].copy()
-        done = packed[:, 2 * d + k + 1] != 0
-        reason = packed[:, 2 * d + k + 2].astype(np.int32)
-        return obs, rew, done, self._infos(terms, reason, done, tobs)
-
-    def step(self, actions):
-        self.step_async(actions)
-        return self.step_wait()
-
-    def close(self):
-        for e in getattr(self, "engines", []):
-            e.close()
-
-    def seed(self, seed=None):
-        """SB3 VecEnv.seed: env i gets seed + i.  Here: re-keys the engines' counter-based RSI generator (dmg1_set_seed; env index
-        and reset count are part of the key already) and returns the per-env seeds SB3 expects."""
-        if seed is None:
-            return [None] * self.num_envs
-        for k, e in enumerate(self.engines):
-            e.set_seed(int(seed) + 104729 * k)
-        return [int(seed) + i for i in range(self.num_envs)]
-
-    # ---- the rest of SB3's VecEnv surface (same conventions as HipDeepMimicVecEnv: one batch object stands for all envs)
-    def _n_indices(self, indices):
-        return self.num_envs if indices is None else len(np.atleast_1d(indices))
-
-    def get_attr(self, attr_name, indices=None):
-        return [getattr(self, attr_name)] * self._n_indices(indices)
-
-    def set_attr(self, attr_name, value, indices=None):
-        setattr(self, attr_name, value)
-
-    def env_method(self, method_name, *method_args, indices=None, **method_kwargs):
-        return [getattr(self, method_name)(*method_args, **method_kwargs)] * self._n_indices(indices)
-
-    def env_is_wrapped(self, wrapper_class, indices=None):
-        return [False] * self._n_indices(indices)
-
-    def getattr_depth_check(self, name, already_found):
-        return None
-
-    @property
-    def unwrapped(self):
-        return self
-
-    def get_images(self):
-        """One frame per env in SB3; a 4 096-tile mosaic is of no use: the frame of env 0 stands for the batch."""
-        return [self.render(mode="rgb_array")]
-
-    def render(self, mode=None):
-        """Software stick figure (render.py) of env 0 of the batch, 240 x 320 x 3 uint8 — what VecVideoRecorder-style callers get.
-        The forward evaluation that refreshes the body poses puts the warm start back: rendering never changes the physics."""
-        from .render import stick_figure
-        e = self.engine
-        if e._debug is None:
-            e.enable_debug()
-        q, v, w = e.get_state()
-        e.set_state(q, v, warm=w, run_forward=True)
-        e.set_state(q, v, warm=w, run_forward=False)
-        xpos = e._debug[0, :117].double().cpu().numpy().reshape(39, 3)
-        return stick_figure(xpos, self.model.body_parent)
 
 
-class G1DPEnv:
+class G1DPEnv(HipImitationEnv):
     """``DPEnv(motion, robot="unitree_g1")`` (src/deepmimic_env.py:272-510): one environment of the batch engine behind the
     reference's Gym surface; ``deepmimic_env.DPEnv`` constructs this class for the G1 robot."""
 
     version = "v1.0"
+    REASONS = REASONS      # the G1 table has reason 8, the run clip's roll / pitch limit
 
     def __init__(self, motion=None, load_mocap=True, robot="unitree_g1", _profile=False, device=0):
         import random
         import torch
-        from .deepmimic_env import Box, DPEnvConfig
+        from .deepmimic_env import DPEnvConfig
         if robot != "unitree_g1":
             raise ValueError("G1DPEnv is the unitree_g1 environment")
         if not load_mocap:
@@ -533,8 +349,7 @@ class G1DPEnv:
         self._out = self._eng.alloc_outputs()
         self.mocap_dt, self.mocap_data_len = self.mocap.dt, len(self.mocap.data_config)
         self.idx_curr, self.episode_reward, self.episode_length = -1, 0, 0
-        lo, hi = self.model.act_ctrlrange[:NACT, 0].astype(np.float32), self.model.act_ctrlrange[:NACT, 1].astype(np.float32)
-        self.action_space = Box(lo, hi, dtype=np.float32)
+        self.action_space = _action_space(self.model, NACT)
         self.observation_space = Box(-np.inf, np.inf, (NOBS,), np.float64)
         self.reference_state_init()
 
@@ -542,72 +357,12 @@ class G1DPEnv:
         self.idx_init = self._random.randint(0, self.mocap_data_len - 1) if idx_init is None else idx_init
         self.idx_curr = self.idx_init
 
-    def _push(self):
-        t = self._torch
-        self._eng.set_counters(t.tensor([max(self.idx_curr, 0)], dtype=t.int32, device=self._eng.device),
-                               t.tensor([self.episode_length], dtype=t.int32, device=self._eng.device))
-
     def step(self, action, force_state=None):
-        from .deepmimic_env import _make_info
-        t, dev = self._torch, self._eng.device
         action = np.asarray(action, np.float64)
         if action.shape == (NU,):          # the full action vector MujocoEnv.__init__ probes with (:349): hands are dropped
             action = action[:NACT]
         assert action.shape == (NACT,)
-        self._push()
-        if force_state is not None:
-            q, v = force_state
-            self._eng.step_forced(t.tensor(np.asarray(q)[None], dtype=t.float32, device=dev),
-                                  t.tensor(np.asarray(v)[None], dtype=t.float32, device=dev), self._out)
-        else:
-            self._eng.step(t.tensor(action[None], dtype=t.float32, device=dev), self._out)
-        obs = self._out["obs"][0].double().cpu().numpy()
-        reason, done = int(self._out["reason"][0].item()), bool(self._out["done"][0].item())
-        if reason in (5, 6):
-            if reason == 6:
-                self.idx_curr = (self.idx_curr + 1) % self.mocap_data_len
-                self.episode_reward = float(self._eng.get_counters()[2][0].item())
-                self.episode_length += 1
-            return obs, 0, True, {}
-        reward = float(self._out["rew"][0].item())
-        info = _make_info(self._out["terms"][0].cpu().numpy(), reason)
-        if reason == 8:
-            info["done_reason"] = REASONS[8]
-        self.idx_curr = (self.idx_curr + 1) % self.mocap_data_len
-        self.episode_reward += reward
-        self.episode_length += 1
-        return obs, reward, done, info
-
-    def reset(self):
-        self.episode_reward, self.episode_length = 0, 0
-        return self.reset_model()
-
-    def reset_model(self, idx_init=None):
-        t = self._torch
-        self.reference_state_init(idx_init=idx_init)
-        obs = t.zeros(1, NOBS, device=self._eng.device)
-        self._eng.reset(obs, idx_init=t.tensor([self.idx_init], dtype=t.int32, device=self._eng.device))
-        self._eng.set_counters(None, t.tensor([self.episode_length], dtype=t.int32, device=self._eng.device))
-        return obs[0].double().cpu().numpy()
-
-    def set_state(self, qpos, qvel):
-        t = self._torch
-        self._eng.set_state(t.tensor(np.asarray(qpos)[None], dtype=t.float32, device=self._eng.device),
-                            t.tensor(np.asarray(qvel)[None], dtype=t.float32, device=self._eng.device))
-
-    def render(self, mode=None):
-        """Software stick figure (render.py) of the current body poses."""
-        from .render import stick_figure
-        if self._eng._debug is None:
-            self._eng.enable_debug()
-        q, v, w = self._eng.get_state()
-        self._eng.set_state(q, v, warm=w, run_forward=True)     # refresh the derived arrays; the warm start is put back
-        self._eng.set_state(q, v, warm=w, run_forward=False)
-        xpos = self._eng._debug[0, :117].double().cpu().numpy().reshape(39, 3)
-        return stick_figure(xpos, self.model.body_parent)
-
-    def close(self):
-        self._eng.close()
+        return self._imitation_step(action, force_state)
 
 
 # ------------------------------------------------------------------------------------------ DPCombinedEnv on the G1
@@ -631,24 +386,21 @@ class HipG1CombinedVecEnv(HipG1VecEnv):
     """N ``DPCombinedEnv()`` instances — the reference's training environment (src/sb3_ppo.py:277-278): Unitree G1, walk / run /
     getup / to_getup motion state machine, obs 98, 23 actions — as one HIP batch with SubprocVecEnv semantics."""
 
-    OBS_DIM, TERMS_DIM = NOBS_COMBINED, 8
-
     def __init__(self, num_envs, device=0, seed=1234, auto_reset=True, sub_batches=1):
         self.mocaps = None
+        self.robot_config = RobotConfig("unitree_g1")
 
         def make(nk, k):
             e, mocaps = _combined_engine(nk, device, seed + 104729 * k, auto_reset)
             self.mocaps = self.mocaps or mocaps
             return e
-        self._build(num_envs, sub_batches, make, scale=1.0 / 20.0)      # action space = ctrlrange / ACT_SCALE (src/combined_env.py:196-200)
+        # action space = ctrlrange / ACT_SCALE (src/combined_env.py:196-200)
+        HipBatchEnv.__init__(self, num_envs, sub_batches, make, load_g1_model()[0], NOBS_COMBINED, 8, NACT, act_scale=1.0 / 20.0,
+                             infos=_LazyCombinedInfos)
         self.mocap = self.mocaps[0]
 
-    def _infos(self, terms, reason, done, tobs):
-        from .combined_env import _LazyCombinedInfos
-        return _LazyCombinedInfos(terms, reason, done, tobs)
 
-
-class G1CombinedEnv:
+class G1CombinedEnv(HipSingleEnv):
     """``DPCombinedEnv()`` of the reference (src/combined_env.py:102-533) — hard-wired to the Unitree G1 there — as one
     environment of the batch engine; ``combined_env.DPCombinedEnv(robot="unitree_g1")`` constructs this class."""
 
@@ -658,7 +410,6 @@ class G1CombinedEnv:
         import random
         import torch
         from .combined_env import DPCombinedEnvConfig, MTToGetup, PAWalk
-        from .deepmimic_env import Box
         self._torch, self._random, self.verbose = torch, random, verbose
         self.ENV_CFG = DPCombinedEnvConfig()
         self.robot = "unitree_g1"
@@ -672,6 +423,7 @@ class G1CombinedEnv:
         self._out = self._eng.alloc_outputs()
         self.episode_reward, self.episode_length, self.debug_n_bad_angles = 0, 0, 0
         self.current_motion_n_steps, self.current_motion_mocap, self.current_player_action = None, None, PAWalk()
+        # divided, where the batch class multiplies by 1 / 20: the two bounds differ in the last bit and both stay as they were
         lo, hi = self.model.act_ctrlrange[:NACT, 0].astype(np.float32) / 20.0, self.model.act_ctrlrange[:NACT, 1].astype(np.float32) / 20.0
         self.action_space = Box(lo, hi, dtype=np.float32)
         self.observation_space = Box(-np.inf, np.inf, (NOBS_COMBINED,), np.float64)
@@ -687,15 +439,8 @@ class G1CombinedEnv:
         self.current_motion_mocap = motion
         self.current_motion_n_steps = 0
 
-    def _push(self):
-        t, dev = self._torch, self._eng.device
-        self._eng.set_motion(t.tensor([self._motion_id()], dtype=t.int32, device=dev))
-        self._eng.set_counters(t.tensor([self.current_motion_n_steps], dtype=t.int32, device=dev),
-                               t.tensor([self.episode_length], dtype=t.int32, device=dev))
-
     def reset(self, rsi=True):
         from .combined_env import PAWalk
-        t, dev = self._torch, self._eng.device
         if rsi:   # :219-227
             if self._random.randint(0, 1) == 0:
                 self.current_motion_mocap = self.walk_mocap
@@ -707,55 +452,29 @@ class G1CombinedEnv:
             self.current_motion_mocap, self.current_motion_n_steps = self.getup_mocap, 0
         self.current_player_action = PAWalk()
         self.episode_reward, self.episode_length = 0, 0
-        self._eng.set_motion(t.tensor([self._motion_id()], dtype=t.int32, device=dev))
-        obs = t.zeros(1, NOBS_COMBINED, device=dev)
-        self._eng.reset(obs, idx_init=t.tensor([self.current_motion_n_steps], dtype=t.int32, device=dev))
+        self._eng.set_motion(self._i32(self._motion_id()))
+        obs = self._torch.zeros(1, NOBS_COMBINED, device=self._eng.device)
+        self._eng.reset(obs, idx_init=self._i32(self.current_motion_n_steps))
         return obs[0].double().cpu().numpy()
 
     def step(self, action, force_state=None):
-        t, dev = self._torch, self._eng.device
         action = np.asarray(action, np.float64)
         if action.shape == (NU,):
             action = action[:NACT]
         assert action.shape == (NACT,)
-        self._push()
-        if force_state is not None:
-            q, v = force_state
-            self._eng.step_forced(t.tensor(np.asarray(q)[None], dtype=t.float32, device=dev),
-                                  t.tensor(np.asarray(v)[None], dtype=t.float32, device=dev), self._out)
-        else:
-            self._eng.step(t.tensor(action[None], dtype=t.float32, device=dev), self._out)
-        obs = self._out["obs"][0].double().cpu().numpy()
-        reason, done = int(self._out["reason"][0].item()), bool(self._out["done"][0].item())
+        self._eng.set_motion(self._i32(self._motion_id()))
+        self._eng.set_counters(self._i32(self.current_motion_n_steps), self._i32(self.episode_length))
+        obs, reason, done = self._drive(action, force_state)
         if reason == 5:
             return obs, 0, True, {}
         terms = self._out["terms"][0].cpu().numpy()
         self.current_motion_mocap = self._motions[int(self._eng.get_motion()[0].item())]
         self.current_motion_n_steps = int(self._eng.get_counters()[0][0].item())
         self.debug_n_bad_angles = int(terms[7])
-        self.episode_length += 1
+        self.episode_length += 1                     # counted on the host; the engine's reward sum is read on reason 6 only
         if reason == 6:
             self.episode_reward = float(self._eng.get_counters()[2][0].item())
             return obs, 0, True, {}
         reward = float(self._out["rew"][0].item())
         self.episode_reward += reward
-        info = {"reward_config": float(terms[0]), "reward_qvel": float(terms[1]), "reward_end_eff": float(terms[2]),
-                "reward_com": float(terms[3]), "reward_joint_limit": float(terms[4]), "imitation_reward": float(terms[5]),
-                "task_reward": float(terms[6])}
-        if REASONS.get(reason):
-            info["done_reason"] = REASONS[reason]
-        return obs, reward, done, info
-
-    def render(self, mode=None):
-        """Software stick figure (render.py) of the current body poses."""
-        from .render import stick_figure
-        if self._eng._debug is None:
-            self._eng.enable_debug()
-        q, v, w = self._eng.get_state()
-        self._eng.set_state(q, v, warm=w, run_forward=True)     # refresh the derived arrays; the warm start is put back
-        self._eng.set_state(q, v, warm=w, run_forward=False)
-        xpos = self._eng._debug[0, :117].double().cpu().numpy().reshape(39, 3)
-        return stick_figure(xpos, self.model.body_parent)
-
-    def close(self):
-        self._eng.close()
+        return obs, reward, done, _combined_info(terms, reason, REASONS)

@@ -242,3 +242,10 @@ def test_every_batch_env_class_has_the_vecenv_surface():
             assert hasattr(cls, name), (cls.__name__, name)
         for name in ("get_attr", "set_attr", "env_method", "env_is_wrapped"):
             assert "indices" in inspect.signature(getattr(cls, name)).parameters, (cls.__name__, name)
+    # one implementation: every name of the surface, and the tensor API under it, is the same function object in all four classes
+    classes = (HipDeepMimicVecEnv, HipCombinedVecEnv, HipG1VecEnv, HipG1CombinedVecEnv)
+    for name in list(SB3VecEnvABC.__abstractmethods__) + NON_ABSTRACT + ["reset_tensor", "step_tensor", "step_sub"]:
+        assert len({id(inspect.getattr_static(cls, name)) for cls in classes}) == 1, name
+    # the one documented override: the G1 classes fork their engines' steps onto streams, the humanoid classes step them in order
+    impl = [inspect.getattr_static(cls, "_step_engines") for cls in classes]
+    assert impl[0] is impl[1] and impl[2] is impl[3] and impl[0] is not impl[2]
