@@ -85,6 +85,9 @@ class DmPpoWideStep(DmPpoStepHead):
                 ("zero_ptr", C.c_void_p), ("zero_floats", C.c_longlong), ("adam_state2", C.c_void_p), ("loss_acc", C.c_void_p)]
 
 
+# floats of the state2 buffer of dm_flat_adam_*: {scratch, step count, DM_ADAM_PARTIALS partial sums} (include/deepmimic_hip.h)
+ADAM_STATE_FLOATS = 2 + 1024
+
 _LIB = None
 
 

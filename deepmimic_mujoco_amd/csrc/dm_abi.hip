@@ -13,11 +13,6 @@
 #include <vector>
 
 #include "dm_kernels.hip"
-#include "dm_ppo.hip"
-#include "dm_policy.hip"
-#include "dm_ppo_mlp.hip"
-#include "dm_ppo_wide.hip"
-#include "dm_sac.hip"
 
 struct DmEngine {
   DmConfig cfg;

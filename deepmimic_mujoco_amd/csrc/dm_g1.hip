@@ -14,6 +14,7 @@
 #undef DmModel
 #include "../../include/deepmimic_g1_hip.h"
 #include "dm_g1_topology.h"
+#include "dm_rng.h"
 
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -239,14 +240,6 @@ __device__ __forceinline__ void quat_to_rpy(const float *q, float *rpy) {
   float s = 2 * (w * y - z * x);
   rpy[1] = asinf(fminf(fmaxf(s, -1.f), 1.f));
   rpy[2] = atan2f(2 * (w * z + x * y), 1 - 2 * (y * y + z * z));
-}
-__device__ __host__ __forceinline__ uint32_t hash32(uint64_t seed, uint32_t env, uint32_t step, uint32_t j) {
-  uint64_t x = seed ^ ((uint64_t)env * 0x9E3779B97F4A7C15ull) ^ ((uint64_t)step * 0xBF58476D1CE4E5B9ull) ^
-               ((uint64_t)j * 0x94D049BB133111EBull);
-  x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull;
-  x ^= x >> 27; x *= 0x94D049BB133111EBull;
-  x ^= x >> 31;
-  return (uint32_t)(x >> 32);
 }
 
 #define SYNC() __syncthreads()
@@ -2212,13 +2205,13 @@ __device__ __forceinline__ bool step_enter(const Launch &P, const Dev &T, const 
     if (TASK) {   // DPCombinedEnv.reset(rsi=True) (:219-227): walk with amnesty or getup, random frame; idx_init keeps the motion
       if (P.idx_init) X.idx_curr = P.idx_init[env] < 0 ? 0 : P.idx_init[env];
       else {
-        X.motion = (hash32(P.seed, env, X.rcnt, 0x5EED) & 1) ? 2 : 0;
+        X.motion = (dm_hash32(P.seed, env, X.rcnt, 0x5EED) & 1) ? 2 : 0;
         X.clip = P.clips[X.motion];
-        X.idx_curr = (int)(hash32(P.seed, env, X.rcnt, 0x5EEE) % (uint32_t)X.clip.L) + (X.motion == 0 ? P.amnesty_steps + 10 : 0);
+        X.idx_curr = (int)(dm_hash32(P.seed, env, X.rcnt, 0x5EEE) % (uint32_t)X.clip.L) + (X.motion == 0 ? P.amnesty_steps + 10 : 0);
       }
       fi = (X.motion == 3) ? 1 : X.idx_curr % X.clip.L;
     } else {
-      fi = P.idx_init ? P.idx_init[env] : (int)(hash32(P.seed, env, X.rcnt, 0x5EED) % (uint32_t)X.clip.L);
+      fi = P.idx_init ? P.idx_init[env] : (int)(dm_hash32(P.seed, env, X.rcnt, 0x5EED) % (uint32_t)X.clip.L);
       fi = fi < 0 ? 0 : (fi >= X.clip.L ? X.clip.L - 1 : fi);
       X.idx_curr = fi;
     }
@@ -2463,12 +2456,12 @@ __device__ __forceinline__ bool task_and_finish(const Launch &P, const Dev &T, c
         }
         int fi;
         if (TASK) {   // DPCombinedEnv.reset(rsi=True) (:219-227)
-          X.motion = (hash32(P.seed, env, X.rcnt, 0x5EED) & 1) ? 2 : 0;
+          X.motion = (dm_hash32(P.seed, env, X.rcnt, 0x5EED) & 1) ? 2 : 0;
           X.clip = P.clips[X.motion];
-          X.idx_curr = (int)(hash32(P.seed, env, X.rcnt, 0x5EEE) % (uint32_t)X.clip.L) + (X.motion == 0 ? P.amnesty_steps + 10 : 0);
+          X.idx_curr = (int)(dm_hash32(P.seed, env, X.rcnt, 0x5EEE) % (uint32_t)X.clip.L) + (X.motion == 0 ? P.amnesty_steps + 10 : 0);
           fi = X.idx_curr % X.clip.L;
         } else {
-          fi = (int)(hash32(P.seed, env, X.rcnt, 0x5EED) % (uint32_t)X.clip.L);
+          fi = (int)(dm_hash32(P.seed, env, X.rcnt, 0x5EED) % (uint32_t)X.clip.L);
           X.idx_curr = fi;
         }
         X.rcnt++;

@@ -13,6 +13,7 @@
 // (oracle/dm_oracle.c) is an independent scalar implementation of the same spec.
 #include "../../include/deepmimic_hip.h"
 #include "dm_device.h"
+#include "dm_rng.h"
 #include "dm_topology.h"
 
 #include <math.h>
@@ -224,16 +225,6 @@ __device__ __forceinline__ void quat_to_rpy(const float *q, float *rpy) {
   rpy[0] = atan2f(2 * (w * x + y * z), 1 - 2 * (x * x + y * y));
   rpy[1] = asinf(clampf(2 * (w * y - z * x), -1.f, 1.f));
   rpy[2] = atan2f(2 * (w * z + x * y), 1 - 2 * (y * y + z * z));
-}
-
-// counter-based generator shared with oracle/dm_oracle.c (hash32)
-__device__ __host__ __forceinline__ uint32_t dm_hash32(uint64_t seed, uint32_t env, uint32_t step, uint32_t j) {
-  uint64_t x = seed ^ ((uint64_t)env * 0x9E3779B97F4A7C15ull) ^ ((uint64_t)step * 0xBF58476D1CE4E5B9ull) ^
-               ((uint64_t)j * 0x94D049BB133111EBull);
-  x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull;
-  x ^= x >> 27; x *= 0x94D049BB133111EBull;
-  x ^= x >> 31;
-  return (uint32_t)(x >> 32);
 }
 
 // ---------------------------------------------------------------- narrowphase (per lane)

@@ -20,15 +20,14 @@
 #include <stdint.h>
 
 #include "dm_bf16.h"
+#include "dm_launch.h"
+#include "dm_pol_tile.h"
+#include "dm_rng.h"
 
 namespace {
 
-constexpr int POL_R = 32;          // batch rows per workgroup
 constexpr int POL_THREADS = 256;   // four waves
 constexpr int POL_CHUNK = 128;     // layer-2 columns per chunk (one 32-column tile per wave)
-constexpr int POL_PAD = 4;         // LDS row padding in floats: keeps 16-byte alignment and spreads rows over the banks
-
-typedef float pol_f16v __attribute__((ext_vector_type(16)));
 
 struct PolArgs {
   const float *obs;                 // [N, D]
@@ -43,87 +42,6 @@ struct PolArgs {
   float *mean_out, *act_env, *logp, *val;
   void *act, *obs_copy;            // rollout-buffer rows of the kernel's storage type: float, or bf16 as unsigned short
 };
-
-__device__ __forceinline__ unsigned pol_hash32(unsigned long long seed, unsigned a, unsigned b, unsigned c) {
-  unsigned long long x = seed ^ ((unsigned long long)a * 0x9E3779B97F4A7C15ull) ^ ((unsigned long long)b * 0xBF58476D1CE4E5B9ull) ^
-                         ((unsigned long long)c * 0x94D049BB133111EBull);
-  x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull;
-  x ^= x >> 27; x *= 0x94D049BB133111EBull;
-  x ^= x >> 31;
-  return (unsigned)(x >> 32);
-}
-
-// acc += X[32 x 8 (kb1 - kb0)] W^T for one 32-neuron tile; xs = LDS activations (row stride sx), P = the tile's packed
-// weights (64 float4 per k-block of 8).
-template <int U>
-__device__ __forceinline__ void pol_load(const float4 *p, const float *xrow, int kb, float4 (&w)[U], float4 (&a)[U]) {
-#pragma unroll
-  for (int u = 0; u < U; u++) w[u] = p[(size_t)(kb + u) * 64];
-#pragma unroll
-  for (int u = 0; u < U; u++) a[u] = *reinterpret_cast<const float4 *>(xrow + (kb + u) * 8);
-}
-template <int U>
-__device__ __forceinline__ void pol_mfma(const float4 (&w)[U], const float4 (&a)[U], pol_f16v &acc) {
-#pragma unroll
-  for (int u = 0; u < U; u++) {
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u].x, w[u].x, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u].y, w[u].y, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u].z, w[u].z, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u].w, w[u].w, acc, 0, 0, 0);
-  }
-}
-// first weight batch of a tile, issued early (before the barrier that publishes the tile's activations: the weight
-// stream does not depend on them), consumed by pol_tile_pre
-template <int U>
-__device__ __forceinline__ void pol_prefetch(const float4 *P, int lane, int kb0, float4 (&w)[U]) {
-#pragma unroll
-  for (int u = 0; u < U; u++) w[u] = P[(size_t)(kb0 + u) * 64 + lane];
-}
-template <int U, bool PRE>
-__device__ __forceinline__ void pol_tile_impl(const float *xs, int sx, const float4 *P, int lane, int kb0, int kb1, pol_f16v &acc,
-                                              float4 (&wA)[U]) {
-  const float *xrow = xs + (lane & 31) * sx + 4 * (lane >> 5);
-  const float4 *p = P + lane;
-  const int nb = (kb1 - kb0) / U;
-  // ping-pong over two register sets (no copies): the loads of batch it + 1 are in flight under the 4 U MFMAs of batch
-  // it, and the MFMAs wait only for their own batch (s_waitcnt vmcnt(U))
-  float4 aA[U], wB[U], aB[U];
-  if (nb > 0) {
-    if (PRE) {
-#pragma unroll
-      for (int u = 0; u < U; u++) aA[u] = *reinterpret_cast<const float4 *>(xrow + (kb0 + u) * 8);
-    } else {
-      pol_load<U>(p, xrow, kb0, wA, aA);
-    }
-  }
-  int it = 0;
-  for (; it + 2 <= nb; it += 2) {
-    pol_load<U>(p, xrow, kb0 + (it + 1) * U, wB, aB);
-    pol_mfma<U>(wA, aA, acc);
-    if (it + 2 < nb) pol_load<U>(p, xrow, kb0 + (it + 2) * U, wA, aA);
-    pol_mfma<U>(wB, aB, acc);
-  }
-  if (it < nb) pol_mfma<U>(wA, aA, acc);
-  for (int kb = kb0 + nb * U; kb < kb1; kb++) {
-    const float4 w = p[(size_t)kb * 64];
-    const float4 a = *reinterpret_cast<const float4 *>(xrow + kb * 8);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, w.x, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, w.y, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, w.z, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, w.w, acc, 0, 0, 0);
-  }
-}
-template <int U>
-__device__ __forceinline__ void pol_tile(const float *xs, int sx, const float4 *P, int lane, int kb0, int kb1, pol_f16v &acc) {
-  float4 wA[U];
-  pol_tile_impl<U, false>(xs, sx, P, lane, kb0, kb1, acc, wA);
-}
-// the first batch's weights (kb0 .. kb0 + U - 1; requires kb1 - kb0 >= U) were fetched by pol_prefetch<U>
-template <int U>
-__device__ __forceinline__ void pol_tile_pre(const float *xs, int sx, const float4 *P, int lane, int kb0, int kb1, pol_f16v &acc,
-                                             float4 (&wpre)[U]) {
-  pol_tile_impl<U, true>(xs, sx, P, lane, kb0, kb1, acc, wpre);
-}
 
 // hs[row][o0 + r] = tanh(acc + bias)
 __device__ __forceinline__ void pol_store_tanh(const pol_f16v &acc, const float *bias, int o0, float *hs, int sh, int col0, int lane) {
@@ -250,13 +168,9 @@ __global__ void __launch_bounds__(POL_THREADS) pol_forward_kernel(PolArgs a) {
     if (j < a.A) {
       float eps[2] = {0.f, 0.f};
       if (!a.deterministic) {
-        const float u1 = ((float)(pol_hash32(a.seed, (unsigned)e, ctr, (unsigned)j) >> 8) + 1.0f) * (1.0f / 16777216.0f);   // (0, 1]
-        const float u2 = (float)(pol_hash32(a.seed, (unsigned)e, ctr, (unsigned)j + 1u) >> 8) * (1.0f / 16777216.0f);
-        const float rad = sqrtf(-2.0f * logf(u1));
-        float sn, cs;
-        sincosf(6.283185307179586f * u2, &sn, &cs);
-        eps[0] = rad * cs;
-        eps[1] = rad * sn;
+        const DmNormal2 n = dm_normal2(a.seed, (unsigned)e, ctr, (unsigned)j);
+        eps[0] = n.e0;
+        eps[1] = n.e1;
       }
       for (int t = 0; t < 2 && j + t < a.A; t++) {
         const int c = j + t;
@@ -279,25 +193,10 @@ __global__ void __launch_bounds__(POL_THREADS) pol_forward_kernel(PolArgs a) {
   if (q == 0 && ok) a.logp[e] = lp;
 }
 
-// W (element (o, k) at W[o so + k sk]; nn.Linear [O x K] row-major is so = K, sk = 1, its transpose so = 1, sk = O) ->
-// P[tile][k-block][lane] float4 = W(32 tile + (lane & 31), 8 kb + 4 (lane >> 5) + 0..3), zero outside O x K
-__device__ __forceinline__ void pol_pack_one(const float *W, int O, int K, int so, int sk, int tiles, int KB, float4 *P, int i) {
-  if (i >= tiles * KB * 64) return;
-  const int lane = i & 63, kb = (i >> 6) % KB, to = (i >> 6) / KB;
-  const int o = to * 32 + (lane & 31), k = kb * 8 + 4 * (lane >> 5);
-  float v[4];
-#pragma unroll
-  for (int c = 0; c < 4; c++) v[c] = (o < O && k + c < K) ? W[(size_t)o * so + (size_t)(k + c) * sk] : 0.f;
-  P[i] = make_float4(v[0], v[1], v[2], v[3]);
-}
 __global__ void pol_pack_kernel(const float *W, int O, int K, int tiles, int KB, float4 *P) {
   pol_pack_one(W, O, K, K, 1, tiles, KB, P, blockIdx.x * blockDim.x + threadIdx.x);
 }
 
-inline int pol_dp(int D) { return (D + 7) & ~7; }
-inline bool pol_dims_ok(int D, int H1, int H2, int A) {
-  return D >= 1 && H1 >= 32 && H2 >= 32 && (H1 % 32) == 0 && (H2 % 32) == 0 && A >= 1 && A <= 32;
-}
 inline size_t pol_lds_bytes(int D, int H1) {
   const int sx = pol_dp(D) + POL_PAD, sc = POL_CHUNK + POL_PAD;
   return (size_t)(POL_R * (sx > sc ? sx : sc) + POL_R * (H1 + POL_PAD)) * sizeof(float);
@@ -306,14 +205,14 @@ inline size_t pol_lds_bytes(int D, int H1) {
 }  // namespace
 
 extern "C" long long dm_policy_packed_floats(int D, int H1, int H2, int A) {
-  if (!pol_dims_ok(D, H1, H2, A)) return -22;
+  if (!pol_dims_ok(D, H1, H2, A)) return DM_EINVAL;
   return 256ll * ((long long)(H1 / 32) * (pol_dp(D) / 8) + (long long)(H2 / 32) * (H1 / 8) + (long long)(H2 / 8));
 }
 
 extern "C" int dm_policy_pack(const float *W1, const float *W2, const float *W3, int D, int H1, int H2, int A, float *packed,
                               void *stream) {
-  if (!W1 || !W2 || !W3 || !packed || !pol_dims_ok(D, H1, H2, A)) return -22;
-  if (pol_lds_bytes(D, H1) > 160 * 1024) return -22;
+  if (!W1 || !W2 || !W3 || !packed || !pol_dims_ok(D, H1, H2, A)) return DM_EINVAL;
+  if (pol_lds_bytes(D, H1) > 160 * 1024) return DM_EINVAL;
   hipStream_t s = (hipStream_t)stream;
   float4 *P1 = reinterpret_cast<float4 *>(packed);
   const int T1 = H1 / 32, KB1 = pol_dp(D) / 8, T2 = H2 / 32, KB2 = H1 / 8, KB3 = H2 / 8;
@@ -321,7 +220,7 @@ extern "C" int dm_policy_pack(const float *W1, const float *W2, const float *W3,
   hipLaunchKernelGGL(pol_pack_kernel, dim3((T1 * KB1 * 64 + 255) / 256), dim3(256), 0, s, W1, H1, D, T1, KB1, P1);
   hipLaunchKernelGGL(pol_pack_kernel, dim3((T2 * KB2 * 64 + 255) / 256), dim3(256), 0, s, W2, H2, H1, T2, KB2, P2);
   hipLaunchKernelGGL(pol_pack_kernel, dim3((KB3 * 64 + 255) / 256), dim3(256), 0, s, W3, A, H2, 1, KB3, P3);
-  return hipGetLastError() == hipSuccess ? 0 : -5;
+  return dm_launch_status();
 }
 
 template <typename ST>
@@ -332,19 +231,19 @@ static int pol_forward_launch(const float *obs, int N, int D, int H1, int H2, in
                               float *act_env, float *logp, float *val, ST *obs_copy, void *stream) {
   if (!obs || N < 1 || !pol_dims_ok(D, H1, H2, A) || !pi_packed || !pi_b1 || !pi_b2 || !pi_b3 || !vf_packed || !vf_b1 || !vf_b2 ||
       !vf_b3 || !log_std || !counter || !lo || !hi || !act || !act_env || !logp || !val)
-    return -22;
-  if ((reinterpret_cast<uintptr_t>(pi_packed) | reinterpret_cast<uintptr_t>(vf_packed)) & 15) return -22;
+    return DM_EINVAL;
+  if ((reinterpret_cast<uintptr_t>(pi_packed) | reinterpret_cast<uintptr_t>(vf_packed)) & 15) return DM_EINVAL;
   const size_t lds = pol_lds_bytes(D, H1);
-  if (lds > 160 * 1024) return -22;
+  if (lds > 160 * 1024) return DM_EINVAL;
   // hipFuncSetAttribute applies to the CURRENT device (and to this instantiation): remember the raised limit per device ordinal
   static size_t lds_allowed[64];
   int dev_id = 0;
-  if (hipGetDevice(&dev_id) != hipSuccess || dev_id < 0 || dev_id >= 64) return -5;
+  if (hipGetDevice(&dev_id) != hipSuccess || dev_id < 0 || dev_id >= 64) return DM_EHIP;
   const size_t allowed = lds_allowed[dev_id] ? lds_allowed[dev_id] : (size_t)64 * 1024;
   if (lds > allowed) {
     if (hipFuncSetAttribute(reinterpret_cast<const void *>(pol_forward_kernel<ST>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
         hipSuccess)
-      return -5;
+      return DM_EHIP;
     lds_allowed[dev_id] = lds;
   }
   PolArgs a;
@@ -355,7 +254,7 @@ static int pol_forward_launch(const float *obs, int N, int D, int H1, int H2, in
   a.deterministic = deterministic;
   a.mean_out = mean_out; a.act = act; a.act_env = act_env; a.logp = logp; a.val = val; a.obs_copy = obs_copy;
   hipLaunchKernelGGL(pol_forward_kernel<ST>, dim3((N + POL_R - 1) / POL_R, 2), dim3(POL_THREADS), lds, (hipStream_t)stream, a);
-  return hipGetLastError() == hipSuccess ? 0 : -5;
+  return dm_launch_status();
 }
 
 extern "C" int dm_policy_forward(const float *obs, int N, int D, int H1, int H2, int A, const float *pi_packed, const float *pi_b1,

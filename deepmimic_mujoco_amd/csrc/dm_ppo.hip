@@ -13,53 +13,19 @@
 // the kernel is latency-, not bandwidth-bound: what matters is that it is two launches instead of seventy.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <string.h>
 
 #include "dm_bf16.h"
+#include "dm_launch.h"
+#include "dm_pol_tile.h"
+#include "dm_ppo_common.h"
+#include "dm_rng.h"
 
 namespace {
 
 constexpr int PPO_MAXA = 32;     // action dimensions supported (28 here)
 constexpr int PPO_BLOCK = 256;
 
-__device__ __forceinline__ float ppo_wave_sum(float v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
-// block-wide sum of `v`, result valid in thread 0
-__device__ __forceinline__ float ppo_block_sum(float v, float *red) {
-  v = ppo_wave_sum(v);
-  const int w = threadIdx.x >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[w] = v;
-  __syncthreads();
-  float s = 0;
-  if (threadIdx.x == 0)
-    for (int i = 0; i < (int)(blockDim.x >> 6); i++) s += red[i];
-  return s;
-}
-
-// stats[0] = mean(adv), stats[1] = 1 / (std_unbiased(adv) + 1e-8); also clears the accumulators of the main kernel
-__device__ __forceinline__ void ppo_prepare_body(const float *adv, int B, int normalize, float *stats, float *out8, float *grad_log_std,
-                                                 int A) {
-  __shared__ float red[16];
-  float s = 0;
-  for (int i = threadIdx.x; i < B; i += blockDim.x) s += adv[i];
-  const float tot = ppo_block_sum(s, red);
-  __shared__ float mean_s;
-  if (threadIdx.x == 0) mean_s = tot / (float)B;
-  __syncthreads();
-  const float mean = mean_s;
-  float q = 0;
-  for (int i = threadIdx.x; i < B; i += blockDim.x) { const float d = adv[i] - mean; q += d * d; }
-  const float qq = ppo_block_sum(q, red);
-  if (threadIdx.x == 0) {
-    if (normalize && B > 1) { stats[0] = mean; stats[1] = 1.0f / (sqrtf(qq / (float)(B - 1)) + 1e-8f); }
-    else { stats[0] = 0.f; stats[1] = 1.f; }
-  }
-  if (threadIdx.x < 8) out8[threadIdx.x] = 0.f;
-  if (grad_log_std && (int)threadIdx.x < A) grad_log_std[threadIdx.x] = 0.f;
-}
 __global__ void ppo_prepare_kernel(const float *adv, int B, int normalize, float *stats, float *out8, float *grad_log_std, int A) {
   ppo_prepare_body(adv, B, normalize, stats, out8, grad_log_std, A);
 }
@@ -150,7 +116,7 @@ extern "C" int dm_ppo_loss(const float *mean, const float *log_std, const float 
                            float *scratch, void *stream) {
   if (!mean || !log_std || !value || !act || !old_logp || !adv || !ret || !grad_mean || !grad_log_std || !grad_value || !out8 ||
       !scratch || B < 1 || A < 1 || A > PPO_MAXA)
-    return -22;
+    return DM_EINVAL;
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(ppo_prepare_kernel, dim3(1), dim3(1024), 0, s, adv, B, normalize_advantage, scratch, out8, grad_log_std, A);
   const int rows_per_block = 8 * (PPO_BLOCK / 32);            // eight rows per half-wave
@@ -159,7 +125,7 @@ extern "C" int dm_ppo_loss(const float *mean, const float *log_std, const float 
   hipLaunchKernelGGL(ppo_loss_kernel, dim3(loss_blocks), dim3(PPO_BLOCK), 0, s, mean, log_std, value, act,
                      old_logp, adv, ret, B, A, clip_range, vf_coef, ent_coef, scratch, grad_mean, grad_log_std, grad_value, out8);
   hipLaunchKernelGGL(ppo_finish_kernel, dim3(1), dim3(64), 0, s, log_std, A, vf_coef, ent_coef, scratch, grad_log_std, out8);
-  return hipGetLastError() == hipSuccess ? 0 : -5;
+  return dm_launch_status();
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -171,8 +137,6 @@ extern "C" int dm_ppo_loss(const float *mean, const float *log_std, const float 
 // partial tiles are added to dW with float atomics (dW and db zeroed by the caller on the same stream).
 namespace {
 
-typedef float ppo_f16v __attribute__((ext_vector_type(16)));
-
 __device__ __forceinline__ void ppo_wgrad_body(const float *dY, const float *X, float *dW, float *db, int B, int O, int I, int kchunk,
                                                int bx, int by, int bz) {
   const int lane = threadIdx.x, r = lane & 31, h = lane >> 5;
@@ -180,7 +144,7 @@ __device__ __forceinline__ void ppo_wgrad_body(const float *dY, const float *X, 
   const bool oa = (o0 + r) < O, ia = (i0 + r) < I;
   const float *pa = dY + (size_t)(b0 + h) * O + (o0 + r);
   const float *px = X + (size_t)(b0 + h) * I + (i0 + r);
-  ppo_f16v acc;
+  pol_f16v acc;
 #pragma unroll
   for (int j = 0; j < 16; j++) acc[j] = 0.f;
   float dbacc = 0.f;
@@ -218,15 +182,15 @@ __global__ void __launch_bounds__(64) ppo_wgrad_kernel(const float *dY, const fl
 
 // dW [O x I] and db [O] must be zero on entry (stream-ordered).  B must be a multiple of 64.
 extern "C" int dm_linear_wgrad(const float *dY, const float *X, float *dW, float *db, int B, int O, int I, void *stream) {
-  if (!dY || !X || !dW || !db || B < 64 || (B % 64) != 0 || O < 1 || I < 1) return -22;
+  if (!dY || !X || !dW || !db || B < 64 || (B % 64) != 0 || O < 1 || I < 1) return DM_EINVAL;
   const int tiles = ((O + 31) / 32) * ((I + 31) / 32);
   int splitk = 1;
   while (splitk * 2 * tiles <= 1024 && B / (splitk * 2) >= 64 && (B % (splitk * 2 * 64)) == 0) splitk *= 2;
   const int kchunk = B / splitk;                       // multiple of 64 (one unrolled group of the kernel)
-  if (kchunk % 64 != 0) return -22;
+  if (kchunk % 64 != 0) return DM_EINVAL;
   hipLaunchKernelGGL(ppo_wgrad_kernel, dim3((I + 31) / 32, (O + 31) / 32, splitk), dim3(64), 0, (hipStream_t)stream, dY, X, dW, db, B,
                      O, I, kchunk);
-  return hipGetLastError() == hipSuccess ? 0 : -5;
+  return dm_launch_status();
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -257,13 +221,13 @@ __global__ void __launch_bounds__(256) ppo_colsum_kernel(const float *Y, int B, 
 }  // namespace
 
 extern "C" int dm_colsum(const float *Y, int B, int O, float *out, void *stream) {
-  if (!Y || !out || B < 1 || O < 1) return -22;
+  if (!Y || !out || B < 1 || O < 1) return DM_EINVAL;
   const int cb = (O + 63) / 64;
   int slices = 1;
   while (slices * 2 * cb <= 1024 && B / (slices * 2) >= 64) slices *= 2;
   const int rpb = (B + slices - 1) / slices;
   hipLaunchKernelGGL(ppo_colsum_kernel, dim3(cb, slices), dim3(256), 0, (hipStream_t)stream, Y, B, O, rpb, out);
-  return hipGetLastError() == hipSuccess ? 0 : -5;
+  return dm_launch_status();
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -352,7 +316,7 @@ __global__ void __launch_bounds__(256) ppo_linear_tanh_kernel(const float *__res
   __syncthreads();
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, r = lane & 31, h = lane >> 5;
   const int wr = (w & 1) * 32, wc = (w >> 1) * 64;
-  ppo_f16v acc0, acc1;
+  pol_f16v acc0, acc1;
 #pragma unroll
   for (int j = 0; j < 16; j++) acc0[j] = acc1[j] = 0.f;
   const float *xa = xs + (wr + r) * ld + h, *wb0 = ws + (wc + r) * ld + h, *wb1 = ws + (wc + 32 + r) * ld + h;
@@ -413,7 +377,7 @@ __global__ void __launch_bounds__(512) ppo_tanh_wgrad_kernel(const float *__rest
   bool ia[NT];
 #pragma unroll
   for (int t = 0; t < NT; t++) ia[t] = (t * 32 + r) < I;
-  ppo_f16v acc[NT];
+  pol_f16v acc[NT];
 #pragma unroll
   for (int t = 0; t < NT; t++)
 #pragma unroll
@@ -543,25 +507,25 @@ __global__ void __launch_bounds__(256) ppo_tanh_bwd_colsum4_kernel(const float *
 }  // namespace
 
 extern "C" int dm_linear_tanh(const float *X, const float *W, const float *bias, float *Y, int B, int O, int I, void *stream) {
-  if (!X || !W || !bias || !Y || B < 1 || O < 1 || I < 1 || I > LT_MAXI) return -22;
+  if (!X || !W || !bias || !Y || B < 1 || O < 1 || I < 1 || I > LT_MAXI) return DM_EINVAL;
   const size_t lds = (size_t)(LT_ROWS + LT_COLS) * (I | 1) * sizeof(float);         // <= 99 KB at I = 128
   static bool attr_done[64] = {};
   int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return -5;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return DM_EHIP;
   if (!attr_done[dev]) {
     if (hipFuncSetAttribute((const void *)ppo_linear_tanh_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024) != hipSuccess)
-      return -5;
+      return DM_EHIP;
     attr_done[dev] = true;
   }
   hipLaunchKernelGGL(ppo_linear_tanh_kernel, dim3((B + LT_ROWS - 1) / LT_ROWS, (O + LT_COLS - 1) / LT_COLS), dim3(256), lds,
                      (hipStream_t)stream, X, W, bias, Y, B, O, I, ((((uintptr_t)X | (uintptr_t)W) & 15) == 0 && I >= 4) ? 1 : 0);
-  return hipGetLastError() == hipSuccess ? 0 : -5;
+  return dm_launch_status();
 }
 
 // dW [O x I] and db [O] must be zero on entry (stream-ordered).  I <= 128.
 extern "C" int dm_tanh_linear_wgrad(const float *dY, const float *Y, const float *X, float *dW, float *db, int B, int O, int I,
                                     void *stream) {
-  if (!dY || !Y || !X || !dW || !db || B < 1 || O < 1 || I < 1 || I > 128) return -22;
+  if (!dY || !Y || !X || !dW || !db || B < 1 || O < 1 || I < 1 || I > 128) return DM_EINVAL;
   const int ot = (O + 31) / 32, nt = (I + 31) / 32;
   int groups = 1;                                      // workgroups per output tile: enough to cover the chip once
   while (groups * 2 * ot <= 256 && B / (groups * 2) >= 256) groups *= 2;
@@ -574,22 +538,22 @@ extern "C" int dm_tanh_linear_wgrad(const float *dY, const float *Y, const float
     case 3: hipLaunchKernelGGL(ppo_tanh_wgrad_kernel<3>, grid, block, 0, s, dY, Y, X, dW, db, B, O, I, rpg); break;
     default: hipLaunchKernelGGL(ppo_tanh_wgrad_kernel<4>, grid, block, 0, s, dY, Y, X, dW, db, B, O, I, rpg); break;
   }
-  return hipGetLastError() == hipSuccess ? 0 : -5;
+  return dm_launch_status();
 }
 
 // dZ = dY * (1 - Y^2) (dZ may be dY), db[o] += column sums of dZ (db zeroed by the caller, stream-ordered).
 extern "C" int dm_tanh_bwd_colsum(const float *dY, const float *Y, float *dZ, float *db, int B, int O, void *stream) {
-  if (!dY || !Y || !dZ || !db || B < 1 || O < 1) return -22;
+  if (!dY || !Y || !dZ || !db || B < 1 || O < 1) return DM_EINVAL;
   const int cb = (O + 63) / 64;
   if ((O & 3) == 0 && ((uintptr_t)dY & 15) == 0 && ((uintptr_t)Y & 15) == 0 && ((uintptr_t)dZ & 15) == 0) {
     hipLaunchKernelGGL(ppo_tanh_bwd_colsum4_kernel, dim3(cb, (B + 63) / 64), dim3(256), 0, (hipStream_t)stream, dY, Y, dZ, B, O, db);
-    return hipGetLastError() == hipSuccess ? 0 : -5;
+    return dm_launch_status();
   }
   int slices = 1;
   while (slices * 2 * cb <= 2048 && B / (slices * 2) >= 32) slices *= 2;
   const int rpb = (B + slices - 1) / slices;
   hipLaunchKernelGGL(ppo_tanh_bwd_colsum_kernel, dim3(cb, slices), dim3(256), 0, (hipStream_t)stream, dY, Y, dZ, B, O, rpb, db);
-  return hipGetLastError() == hipSuccess ? 0 : -5;
+  return dm_launch_status();
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -640,20 +604,20 @@ __global__ void __launch_bounds__(128) ppo_gather_bf16_kernel(const long long *i
 extern "C" int dm_ppo_gather_bf16(const long long *idx, int B, const unsigned short *obs, int D, const unsigned short *act, int A,
                                   const float *adv, const float *ret, const float *logp, float *o_obs, float *o_act, float *o_adv,
                                   float *o_ret, float *o_logp, void *stream) {
-  if (!idx || B < 1 || !obs || !act || !adv || !ret || !logp || !o_obs || !o_act || !o_adv || !o_ret || !o_logp) return -22;
-  if (D < 1 || A < 1 || D > BF16_ROW_MAX || A > BF16_ROW_MAX) return -22;
+  if (!idx || B < 1 || !obs || !act || !adv || !ret || !logp || !o_obs || !o_act || !o_adv || !o_ret || !o_logp) return DM_EINVAL;
+  if (D < 1 || A < 1 || D > BF16_ROW_MAX || A > BF16_ROW_MAX) return DM_EINVAL;
   hipLaunchKernelGGL(ppo_gather_bf16_kernel, dim3(B), dim3(128), 0, (hipStream_t)stream, idx, B, obs, D, act, A, adv, ret, logp, o_obs,
                      o_act, o_adv, o_ret, o_logp);
-  return hipGetLastError() == hipSuccess ? 0 : -5;
+  return dm_launch_status();
 }
 
 extern "C" int dm_ppo_gather(const long long *idx, int B, const float *obs, int D, const float *act, int A, const float *adv,
                              const float *ret, const float *logp, float *o_obs, float *o_act, float *o_adv, float *o_ret,
                              float *o_logp, void *stream) {
-  if (!idx || B < 1 || !obs || !act || !adv || !ret || !logp || !o_obs || !o_act || !o_adv || !o_ret || !o_logp) return -22;
+  if (!idx || B < 1 || !obs || !act || !adv || !ret || !logp || !o_obs || !o_act || !o_adv || !o_ret || !o_logp) return DM_EINVAL;
   hipLaunchKernelGGL(ppo_gather_kernel, dim3(B), dim3(128), 0, (hipStream_t)stream, idx, B, obs, D, act, A, adv, ret, logp, o_obs,
                      o_act, o_adv, o_ret, o_logp);
-  return hipGetLastError() == hipSuccess ? 0 : -5;
+  return dm_launch_status();
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -754,15 +718,15 @@ __global__ void adam_update_kernel(float *p, const float *g, float *m, float *v,
 static int flat_adam_launch(float *p, const float *g, float *m, float *v, int n, float lr, float beta1, float beta2, float eps,
                             float max_norm, float grad_scale, float *state2, int state2_floats, void *stream, int begin,
                             const DmGatherSpec *next = nullptr, int next_bf16 = 0) {
-  if (!p || !g || !m || !v || !state2 || n < 1 || !(grad_scale > 0.f)) return -22;
-  if (state2_floats < 2 + DM_ADAM_PARTIALS) return -22;   // the partial sums live behind the two scalars: a shorter buffer would be overrun
+  if (!p || !g || !m || !v || !state2 || n < 1 || !(grad_scale > 0.f)) return DM_EINVAL;
+  if (state2_floats < 2 + DM_ADAM_PARTIALS) return DM_EINVAL;   // the partial sums live behind the two scalars: a shorter buffer would be overrun
   AdamGather G;
   memset(&G, 0, sizeof G);
   int gather_blocks = 0;
   if (next) {
     if (!next->idx || next->B < 1 || next->D < 1 || next->A < 1 || !next->obs || !next->act || !next->adv || !next->ret || !next->logp ||
-        !next->o_obs || !next->o_act || !next->o_adv || !next->o_ret || !next->o_logp) return -22;
-    if (next_bf16 && (next->D > BF16_ROW_MAX || next->A > BF16_ROW_MAX)) return -22;
+        !next->o_obs || !next->o_act || !next->o_adv || !next->o_ret || !next->o_logp) return DM_EINVAL;
+    if (next_bf16 && (next->D > BF16_ROW_MAX || next->A > BF16_ROW_MAX)) return DM_EINVAL;
     G.idx = next->idx; G.B = next->B; G.D = next->D; G.A = next->A;
     G.obs = next->obs; G.act = next->act; G.adv = next->adv; G.ret = next->ret; G.logp = next->logp;
     G.o_obs = next->o_obs; G.o_act = next->o_act; G.o_adv = next->o_adv; G.o_ret = next->o_ret; G.o_logp = next->o_logp;
@@ -775,7 +739,7 @@ static int flat_adam_launch(float *p, const float *g, float *m, float *v, int n,
   if (next && next_bf16) hipLaunchKernelGGL(adam_sumsq_kernel<unsigned short>, dim3(blocks + gather_blocks), dim3(256), 0, s, g, n, state2, begin, blocks, G);
   else hipLaunchKernelGGL(adam_sumsq_kernel<float>, dim3(blocks + gather_blocks), dim3(256), 0, s, g, n, state2, begin, blocks, G);
   hipLaunchKernelGGL(adam_update_kernel, dim3(blocks), dim3(256), 0, s, p, g, m, v, n, lr, beta1, beta2, eps, max_norm, grad_scale, state2);
-  return hipGetLastError() == hipSuccess ? 0 : -5;
+  return dm_launch_status();
 }
 extern "C" int dm_flat_adam_step(float *p, const float *g, float *m, float *v, int n, float lr, float beta1, float beta2, float eps,
                                  float max_norm, float grad_scale, float *state2, int state2_floats, void *stream) {
@@ -794,7 +758,7 @@ extern "C" int dm_flat_adam_step_gather(float *p, const float *g, float *m, floa
 extern "C" int dm_flat_adam_step_gather_bf16(float *p, const float *g, float *m, float *v, int n, float lr, float beta1, float beta2,
                                              float eps, float max_norm, float grad_scale, float *state2, int state2_floats, int begin,
                                              const DmGatherSpecBf16 *next, void *stream) {
-  if (!next) return -22;
+  if (!next) return DM_EINVAL;
   DmGatherSpec sp;
   sp.idx = next->idx; sp.B = next->B; sp.D = next->D; sp.A = next->A; sp.reserved = 0;
   sp.obs = reinterpret_cast<const float *>(next->obs); sp.act = reinterpret_cast<const float *>(next->act);   // retyped in the kernel
@@ -809,15 +773,6 @@ extern "C" int dm_flat_adam_step_gather_bf16(float *p, const float *g, float *m,
 // step's data go into the rollout buffer.  Two launches instead of ~20 elementwise PyTorch kernels.
 namespace {
 
-__device__ __forceinline__ unsigned ppo_hash32(unsigned long long seed, unsigned a, unsigned b, unsigned c) {
-  unsigned long long x = seed ^ ((unsigned long long)a * 0x9E3779B97F4A7C15ull) ^ ((unsigned long long)b * 0xBF58476D1CE4E5B9ull) ^
-                         ((unsigned long long)c * 0x94D049BB133111EBull);
-  x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull;
-  x ^= x >> 27; x *= 0x94D049BB133111EBull;
-  x ^= x >> 31;
-  return (unsigned)(x >> 32);
-}
-
 // act = mean + exp(log_std) * eps, eps ~ N(0,1) (Box-Muller on a counter-based hash: env, draw counter, action index);
 // logp = sum_j -0.5 eps_j^2 - log_std_j - 0.5 log(2 pi); act_env = clamp(act, lo, hi).  counter[0] is read here and
 // advanced by ppo_store_kernel, which runs later on the same stream.
@@ -829,12 +784,8 @@ __global__ void ppo_sample_kernel(const float *mean, const float *log_std, int N
   const unsigned ctr = counter[0];
   float lp = 0.f;
   for (int j = 0; j < A; j += 2) {
-    const float u1 = ((float)(ppo_hash32(seed, (unsigned)e, ctr, (unsigned)j) >> 8) + 1.0f) * (1.0f / 16777216.0f);   // (0, 1]
-    const float u2 = (float)(ppo_hash32(seed, (unsigned)e, ctr, (unsigned)j + 1u) >> 8) * (1.0f / 16777216.0f);
-    const float rad = sqrtf(-2.0f * logf(u1));
-    float sn, cs;
-    sincosf(6.283185307179586f * u2, &sn, &cs);
-    const float eps[2] = {rad * cs, rad * sn};
+    const DmNormal2 n = dm_normal2(seed, (unsigned)e, ctr, (unsigned)j);
+    const float eps[2] = {n.e0, n.e1};
     for (int q = 0; q < 2 && j + q < A; q++) {
       const float ls = log_std[j + q];
       const float a = mean[(size_t)e * A + j + q] + expf(ls) * eps[q];
@@ -880,10 +831,10 @@ __global__ void ppo_store_kernel(int N, int D, int A, const float *last_obs, con
 extern "C" int dm_policy_sample(const float *mean, const float *log_std, int N, int A, unsigned long long seed,
                                 const unsigned *counter, const float *lo, const float *hi, float *act, float *act_env,
                                 float *logp, void *stream) {
-  if (!mean || !log_std || !counter || !lo || !hi || !act || !act_env || !logp || N < 1 || A < 1) return -22;
+  if (!mean || !log_std || !counter || !lo || !hi || !act || !act_env || !logp || N < 1 || A < 1) return DM_EINVAL;
   hipLaunchKernelGGL(ppo_sample_kernel, dim3((N + 255) / 256), dim3(256), 0, (hipStream_t)stream, mean, log_std, N, A, seed, counter,
                      lo, hi, act, act_env, logp);
-  return hipGetLastError() == hipSuccess ? 0 : -5;
+  return dm_launch_status();
 }
 
 extern "C" int dm_rollout_store(int N, int D, int A, const float *last_obs, const float *act, const float *val, const float *logp,
@@ -892,10 +843,10 @@ extern "C" int dm_rollout_store(int N, int D, int A, const float *last_obs, cons
                                 void *stream) {
   if (N < 1 || !last_obs || !act || !val || !logp || !rew || !done || !new_obs || !b_obs || !b_act || !b_val || !b_logp || !b_rew ||
       !b_done || !last_obs_out)
-    return -22;
+    return DM_EINVAL;
   hipLaunchKernelGGL(ppo_store_kernel<float>, dim3(N), dim3(128), 0, (hipStream_t)stream, N, D, A, last_obs, act, val, logp, rew, done,
                      new_obs, b_obs, b_act, b_val, b_logp, b_rew, b_done, last_obs_out, counter);
-  return hipGetLastError() == hipSuccess ? 0 : -5;
+  return dm_launch_status();
 }
 
 extern "C" int dm_rollout_store_bf16(int N, int D, int A, const float *last_obs, const float *act, const float *val, const float *logp,
@@ -904,10 +855,10 @@ extern "C" int dm_rollout_store_bf16(int N, int D, int A, const float *last_obs,
                                      float *last_obs_out, unsigned *counter, void *stream) {
   if (N < 1 || D < 1 || A < 1 || !last_obs || !act || !val || !logp || !rew || !done || !new_obs || !b_obs || !b_act || !b_val || !b_logp ||
       !b_rew || !b_done || !last_obs_out)
-    return -22;
+    return DM_EINVAL;
   hipLaunchKernelGGL(ppo_store_kernel<unsigned short>, dim3(N), dim3(128), 0, (hipStream_t)stream, N, D, A, last_obs, act, val, logp, rew,
                      done, new_obs, b_obs, b_act, b_val, b_logp, b_rew, b_done, last_obs_out, counter);
-  return hipGetLastError() == hipSuccess ? 0 : -5;
+  return dm_launch_status();
 }
 
 // ---- dm_rollout_finish: what follows the T env steps of a rollout, as one call — SB3's RolloutBuffer.compute_returns_and_advantage
@@ -1142,7 +1093,7 @@ __global__ void __launch_bounds__(RF_BLOCK) rollout_monitor_kernel(int T, int N,
 }  // namespace
 
 extern "C" long long dm_rollout_finish_workspace_bytes(int T, int N) {
-  if (T < 1 || N < 1) return -22;
+  if (T < 1 || N < 1) return DM_EINVAL;
   const long long nb = (N + RF_BLOCK - 1) / RF_BLOCK;
   return 16 + nb * RF_PART * 8 + (long long)T * nb * 4;                    // head (padded to 16) | block partials | counts
 }
@@ -1151,10 +1102,10 @@ extern "C" int dm_rollout_finish(int T, int N, const float *rew, const void *don
                                  const float *last_val, double gamma, double gae_lambda, float *adv, float *ret, float *ep_acc,
                                  float *ep_hist, unsigned *ep_count, double *stats, void *work, long long work_bytes, void *stream) {
   if (T < 1 || N < 1 || !rew || !done || !val || !last_val || !adv || !ret || !ep_acc || !ep_hist || !ep_count || !stats || !work)
-    return -22;
+    return DM_EINVAL;
   if ((long long)T * ((N + RF_BLOCK - 1) / RF_BLOCK) > 0x7fffffffLL || ((uintptr_t)work & 15) ||
       work_bytes < dm_rollout_finish_workspace_bytes(T, N))
-    return -22;
+    return DM_EINVAL;
   const int nb = (N + RF_BLOCK - 1) / RF_BLOCK;
   unsigned *head = (unsigned *)work;
   double *part = (double *)((char *)work + 16);
@@ -1174,5 +1125,5 @@ extern "C" int dm_rollout_finish(int T, int N, const float *rew, const void *don
   else
     hipLaunchKernelGGL(rollout_monitor_kernel<float>, dim3(nb), dim3(RF_BLOCK), 0, s, T, N, rew, (const float *)done, cnt, head, ep_acc,
                        ep_hist);
-  return hipGetLastError() == hipSuccess ? 0 : -5;
+  return dm_launch_status();
 }

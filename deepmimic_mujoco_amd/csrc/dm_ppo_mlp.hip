@@ -15,12 +15,14 @@
 //                        atomics; one extra block sums the loss partials (loss scalar, entropy gradient)        (1 launch)
 // All products are v_mfma_f32_32x32x2f32 (fp32 in, fp32 accumulate).  Gradients are ACCUMULATED into caller-owned
 // buffers that must be zero on entry (the optimizer's flat gradient arena: pass it as zero_ptr, or clear it on the stream).
-// Included by dm_abi.hip after dm_ppo.hip and dm_policy.hip (uses their device helpers).
+// The tile loop and the weight packing are dm_pol_tile.h (shared with dm_policy.hip), the advantage statistics dm_ppo_common.h.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
 
-#include "../../include/deepmimic_hip.h"
+#include "dm_launch.h"
+#include "dm_pol_tile.h"
+#include "dm_ppo_common.h"
 
 namespace {
 
@@ -31,37 +33,6 @@ struct MlpPackArgs {
   const float *adv; int B, normalize; float *stats, *out8;
   float *zero_ptr; long long zero_floats; float *adam_state2;
 };
-
-// Advantage statistics of the minibatch by ONE block of 256 threads (stats[0] = mean, stats[1] = 1 / (std_unbiased + 1e-8)), as
-// ppo_prepare_body, but with every load of the block in flight at once: the values are read into registers by independent
-// loads instead of 2 x B / 256 dependent round trips — this block is the critical path of the launch.  B <= 8192.
-__device__ __forceinline__ void mlp_adv_stats(const float *adv, int B, int normalize, float *stats, float *out8) {
-  __shared__ float red[16];
-  __shared__ float mean_s;
-  constexpr int ITEMS = 32;
-  float v[ITEMS];
-#pragma unroll
-  for (int k = 0; k < ITEMS; k++) {
-    const int i = threadIdx.x + k * 256;
-    v[k] = (i < B) ? adv[i] : 0.f;
-  }
-  float s = 0.f;
-#pragma unroll
-  for (int k = 0; k < ITEMS; k++) s += v[k];
-  const float tot = ppo_block_sum(s, red);
-  if (threadIdx.x == 0) mean_s = tot / (float)B;
-  __syncthreads();
-  const float mean = mean_s;
-  float q = 0.f;
-#pragma unroll
-  for (int k = 0; k < ITEMS; k++) { const float d = v[k] - mean; q += ((int)threadIdx.x + k * 256 < B) ? d * d : 0.f; }
-  const float qq = ppo_block_sum(q, red);
-  if (threadIdx.x == 0) {
-    if (normalize && B > 1) { stats[0] = mean; stats[1] = 1.0f / (sqrtf(qq / (float)(B - 1)) + 1e-8f); }
-    else { stats[0] = 0.f; stats[1] = 1.f; }
-  }
-  if (threadIdx.x < 8) out8[threadIdx.x] = 0.f;
-}
 
 __global__ void __launch_bounds__(256) mlp_pack_kernel(MlpPackArgs a) {
   const int blk = blockIdx.x;
@@ -82,10 +53,6 @@ __global__ void __launch_bounds__(256) mlp_pack_kernel(MlpPackArgs a) {
   const MlpPackJob &J = a.j[q];
   pol_pack_one(J.W, J.O, J.K, J.so, J.sk, J.tiles, J.KB, J.P, (blk - J.first) * 256 + (int)threadIdx.x);
 }
-
-// tanh(x) = 1 - 2 / (1 + e^{2x}) on the hardware exp / rcp: absolute error ~1e-7 (the accurate tanhf costs ~40 instructions
-// and the forward evaluates 12 k of them per workgroup)
-__device__ __forceinline__ float mlp_tanh(float x) { return 1.f - __fdividef(2.f, 1.f + __expf(2.f * x)); }
 
 struct MlpTrainArgs {
   int B, D, Dp, H1, H2, A;
@@ -161,7 +128,7 @@ __global__ void __launch_bounds__(MLP_THREADS) mlp_fwdbwd_kernel(MlpTrainArgs a)
 #pragma unroll
     for (int j = 0; j < 16; j++) {
       const int row = (j >> 2) * 8 + h * 4 + (j & 3);
-      const float v = mlp_tanh(acc[j] + b);
+      const float v = ppo_fast_tanh(acc[j] + b);
       h1[row * s1 + to * 32 + r] = v;
     }
   }
@@ -194,7 +161,7 @@ __global__ void __launch_bounds__(MLP_THREADS) mlp_fwdbwd_kernel(MlpTrainArgs a)
 #pragma unroll
       for (int j = 0; j < 16; j++) {
         const int row = (j >> 2) * 8 + h * 4 + (j & 3);
-        const float v = mlp_tanh(acc[j] + red[tile * 1024 + j * 64 + lane] + b);
+        const float v = ppo_fast_tanh(acc[j] + red[tile * 1024 + j * 64 + lane] + b);
         h2[row * s2 + tile * 32 + r] = v;
       }
     }
@@ -516,33 +483,33 @@ inline MlpWsLayout mlp_layout(int B, int D, int H1, int H2, int A) {
 }  // namespace
 
 extern "C" long long dm_ppo_mlp_workspace_floats(int B, int D, int H1, int H2, int A) {
-  if (!mlp_dims_ok(B, D, H1, H2, A)) return -22;
-  if (mlp_lds_bytes(D, H1, H2) > 160 * 1024) return -22;
+  if (!mlp_dims_ok(B, D, H1, H2, A)) return DM_EINVAL;
+  if (mlp_lds_bytes(D, H1, H2) > 160 * 1024) return DM_EINVAL;
   return (long long)mlp_layout(B, D, H1, H2, A).total;
 }
 
 extern "C" int dm_ppo_mlp_grad(const DmPpoMlpStep *s, void *stream) {
-  if (!s) return -22;
+  if (!s) return DM_EINVAL;
   const int B = s->B, D = s->D, H1 = s->H1, H2 = s->H2, A = s->A;
-  if (!mlp_dims_ok(B, D, H1, H2, A)) return -22;
-  if (!s->obs || !s->act || !s->adv || !s->ret || !s->old_logp || !s->log_std || !s->g_log_std || !s->out8 || !s->workspace) return -22;
+  if (!mlp_dims_ok(B, D, H1, H2, A)) return DM_EINVAL;
+  if (!s->obs || !s->act || !s->adv || !s->ret || !s->old_logp || !s->log_std || !s->g_log_std || !s->out8 || !s->workspace) return DM_EINVAL;
   for (int t = 0; t < 2; t++)
     for (int l = 0; l < 3; l++)
-      if (!s->W[t][l] || !s->b[t][l] || !s->gW[t][l] || !s->gb[t][l]) return -22;
-  if (reinterpret_cast<uintptr_t>(s->workspace) & 15) return -22;
+      if (!s->W[t][l] || !s->b[t][l] || !s->gW[t][l] || !s->gb[t][l]) return DM_EINVAL;
+  if (reinterpret_cast<uintptr_t>(s->workspace) & 15) return DM_EINVAL;
   const MlpWsLayout L = mlp_layout(B, D, H1, H2, A);
-  if (s->workspace_floats < (long long)L.total) return -22;
+  if (s->workspace_floats < (long long)L.total) return DM_EINVAL;
   const size_t lds = mlp_lds_bytes(D, H1, H2);
-  if (lds > 160 * 1024) return -22;
+  if (lds > 160 * 1024) return DM_EINVAL;
   // hipFuncSetAttribute applies to the CURRENT device: remember the raised limit per device ordinal
   static size_t lds_allowed[64];
   int dev_id = 0;
-  if (hipGetDevice(&dev_id) != hipSuccess || dev_id < 0 || dev_id >= 64) return -5;
+  if (hipGetDevice(&dev_id) != hipSuccess || dev_id < 0 || dev_id >= 64) return DM_EHIP;
   const size_t allowed = lds_allowed[dev_id] ? lds_allowed[dev_id] : (size_t)64 * 1024;
   if (lds > allowed) {
     if (hipFuncSetAttribute(reinterpret_cast<const void *>(mlp_fwdbwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
         hipSuccess)
-      return -5;
+      return DM_EHIP;
     lds_allowed[dev_id] = lds;
   }
   hipStream_t st = (hipStream_t)stream;
@@ -595,7 +562,7 @@ extern "C" int dm_ppo_mlp_grad(const DmPpoMlpStep *s, void *stream) {
   static const int sk_env = getenv("DM_WGRAD_SPLITK") ? atoi(getenv("DM_WGRAD_SPLITK")) : 8;   // workgroup-level split-K (experiments)
   int splitk = s->reserved > 0 ? s->reserved : (sk_env > 0 ? sk_env : 8);
   while (splitk > 1 && (B % (splitk * 8 * WG3_U)) != 0) splitk >>= 1;                         // kchunk / 4 a multiple of 2 WG3_U
-  if ((B % (splitk * 8 * WG3_U)) != 0) return -22;
+  if ((B % (splitk * 8 * WG3_U)) != 0) return DM_EINVAL;
   auto add_wg = [&](const float *dY, const float *X, float *dW, float *db, int O, int I) {
     MlpWgradJob &J = wa.j[nq++];
     J.dY = dY; J.X = X; J.dW = dW; J.db = db; J.O = O; J.I = I; J.nro = (O + 63) / 64; J.nri = (I + 63) / 64;
@@ -612,11 +579,11 @@ extern "C" int dm_ppo_mlp_grad(const DmPpoMlpStep *s, void *stream) {
   wa.B = B; wa.nblocks = nw; wa.log_std = s->log_std; wa.stats = stats; wa.g_log_std = s->g_log_std; wa.out8 = s->out8; wa.loss_acc = s->loss_acc; wa.A = A; wa.part = stats + 8; wa.nwg = B / POL_R;
   wa.vf_coef = s->vf_coef; wa.ent_coef = s->ent_coef;
   hipLaunchKernelGGL(mlp_wgrad_kernel, dim3(nw + 1), dim3(256), 0, st, wa);
-  return hipGetLastError() == hipSuccess ? 0 : -5;
+  return dm_launch_status();
 }
 
 #ifdef MLP_PROFILE
 extern "C" int dm_ppo_mlp_prof(long long *host128) {
-  return hipMemcpyFromSymbol(host128, HIP_SYMBOL(mlp_prof_buf), sizeof(long long) * MLP_NW * 16) == hipSuccess ? 0 : -5;
+  return hipMemcpyFromSymbol(host128, HIP_SYMBOL(mlp_prof_buf), sizeof(long long) * MLP_NW * 16) == hipSuccess ? DM_OK : DM_EHIP;
 }
 #endif

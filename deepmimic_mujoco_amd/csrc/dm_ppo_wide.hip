@@ -24,18 +24,22 @@
 // base + lane * 16 bytes: eight full 128-byte lines.  (Row-major operands made every load touch 32 lines for 32 bytes each and lean
 // on the 32 KB vector L1 to hold 512 half-used lines across k-steps: 92 us for the chain, 58 us for the weight gradients; now 43 + 38.)
 // fp32 master weights, fp32 loss arithmetic, fp32 gradients and Adam; bf16 operands of the products only (north_star: "MFMA used
-// only for the policy-MLP GEMMs").  Included by dm_abi.hip after dm_ppo_mlp.hip.
+// only for the policy-MLP GEMMs").
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <string.h>
 
-#include "../../include/deepmimic_hip.h"
+#include "dm_bf16.h"
+#include "dm_launch.h"
+#include "dm_ppo_common.h"
 
 namespace {
 
 typedef short wide_b8 __attribute__((ext_vector_type(8)));      // 8 bf16 = one MFMA operand fragment (4 VGPRs)
 typedef float wide_f16 __attribute__((ext_vector_type(16)));    // 32 x 32 accumulator: col = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
 
-__device__ __forceinline__ unsigned short wide_f2bf(float x) {  // round to nearest even
+// round to nearest even WITHOUT the NaN branch of bf16_rne (dm_bf16.h): kept apart, merging them changes this file's instructions
+__device__ __forceinline__ unsigned short wide_f2bf(float x) {
   unsigned u = __float_as_uint(x);
   u += 0x7fffu + ((u >> 16) & 1u);
   return (unsigned short)(u >> 16);
@@ -48,8 +52,6 @@ __device__ __forceinline__ unsigned wide_pk2(float a, float b) {
   const wide_bf2 r = __builtin_convertvector(v, wide_bf2);
   return *reinterpret_cast<const unsigned *>(&r);
 }
-__device__ __forceinline__ float wide_bf2f(unsigned short b) { return __uint_as_float((unsigned)b << 16); }
-__device__ __forceinline__ float wide_tanh(float x) { return 1.f - __fdividef(2.f, 1.f + __expf(2.f * x)); }
 __device__ __forceinline__ int wide_row(int reg, int h) { return (reg & 3) + 8 * (reg >> 2) + 4 * h; }
 // fragment order (file header): element index of (n, k) in a matrix with K / 16 = nks k-steps
 __device__ __forceinline__ size_t wide_frag(int n, int k, int nks) {
@@ -83,7 +85,7 @@ struct WidePackArgs {
 __global__ void __launch_bounds__(256) wide_pack_kernel(WidePackArgs a) {
   const int blk = blockIdx.x;
   if (blk == 2 * a.pack_blocks) {
-    if (a.B <= 8192) mlp_adv_stats(a.adv, a.B, a.normalize, a.stats, a.out8);     // every load in flight at once (dm_ppo_mlp.hip)
+    if (a.B <= 8192) mlp_adv_stats(a.adv, a.B, a.normalize, a.stats, a.out8);     // every load in flight at once
     else ppo_prepare_body(a.adv, a.B, a.normalize, a.stats, a.out8, nullptr, 0);
     if (a.adam_state2 && threadIdx.x == 0) { a.adam_state2[0] = 0.f; a.adam_state2[1] += 1.f; }     // Adam's begin
     return;
@@ -227,7 +229,7 @@ __global__ void __launch_bounds__(WIDE_THREADS) wide_fwdbwd_kernel(WideArgs a) {
       for (int q = 0; q < 4; q++) {
         float v[4];
 #pragma unroll
-        for (int i = 0; i < 4; i++) v[i] = wide_tanh(acc[4 * q + i] + bias);
+        for (int i = 0; i < 4; i++) v[i] = ppo_fast_tanh(acc[4 * q + i] + bias);
         wide_put4(H1s, S1, 8 * q + 4 * h, n, a.h1T[trunk], B, b0 + 8 * q + 4 * h, v[0], v[1], v[2], v[3]);
       }
     };
@@ -283,7 +285,7 @@ __global__ void __launch_bounds__(WIDE_THREADS) wide_fwdbwd_kernel(WideArgs a) {
     for (int q = 0; q < 4; q++) {
       float v[4], w[4];
 #pragma unroll
-      for (int i = 0; i < 4; i++) { v[i] = wide_tanh(acc0[4 * q + i] + bias0); w[i] = wide_tanh(acc1[4 * q + i] + bias1); }
+      for (int i = 0; i < 4; i++) { v[i] = ppo_fast_tanh(acc0[4 * q + i] + bias0); w[i] = ppo_fast_tanh(acc1[4 * q + i] + bias1); }
       wide_put4(H2s, S2, 8 * q + 4 * h, n0, a.h2T[trunk], B, b0 + 8 * q + 4 * h, v[0], v[1], v[2], v[3]);
       wide_put4(H2s, S2, 8 * q + 4 * h, n1, a.h2T[trunk], B, b0 + 8 * q + 4 * h, w[0], w[1], w[2], w[3]);
     }
@@ -378,7 +380,7 @@ __global__ void __launch_bounds__(WIDE_THREADS) wide_fwdbwd_kernel(WideArgs a) {
   // extra MFMAs on the critical path: [256,128] 59.6 -> 65.2 us)
   if (a.bias_in_chain && tid < At) {
     float s = 0.f;
-    for (int m = 0; m < WIDE_R; m++) s += wide_bf2f(*reinterpret_cast<const unsigned short *>(dZ3s + m * S3 + 2 * tid));
+    for (int m = 0; m < WIDE_R; m++) s += bf16_widen(*reinterpret_cast<const unsigned short *>(dZ3s + m * S3 + 2 * tid));
     atomicAdd(&a.gb3[trunk][tid], s);
   }
 
@@ -403,8 +405,8 @@ __global__ void __launch_bounds__(WIDE_THREADS) wide_fwdbwd_kernel(WideArgs a) {
 #pragma unroll
       for (int i = 0; i < 4; i++) {
         const int m = 8 * q + 4 * h + i;
-        const float x0 = wide_bf2f(*reinterpret_cast<const unsigned short *>(H2s + m * S2 + 2 * n0));
-        const float x1 = wide_bf2f(*reinterpret_cast<const unsigned short *>(H2s + m * S2 + 2 * n1));
+        const float x0 = bf16_widen(*reinterpret_cast<const unsigned short *>(H2s + m * S2 + 2 * n0));
+        const float x1 = bf16_widen(*reinterpret_cast<const unsigned short *>(H2s + m * S2 + 2 * n1));
         v[i] = acc0[4 * q + i] * (1.f - x0 * x0); w[i] = acc1[4 * q + i] * (1.f - x1 * x1);
       }
       wide_put4(dZ2s, S2, 8 * q + 4 * h, n0, a.dz2T[trunk], B, b0 + 8 * q + 4 * h, v[0], v[1], v[2], v[3]);
@@ -470,7 +472,7 @@ __global__ void __launch_bounds__(WIDE_THREADS) wide_fwdbwd_kernel(WideArgs a) {
         float v[4];
 #pragma unroll
         for (int i = 0; i < 4; i++) {
-          const float x = wide_bf2f(*reinterpret_cast<const unsigned short *>(H1s + (8 * g + 4 * h + i) * S1 + 2 * n));
+          const float x = bf16_widen(*reinterpret_cast<const unsigned short *>(H1s + (8 * g + 4 * h + i) * S1 + 2 * n));
           v[i] = acc[q][4 * g + i] * (1.f - x * x);
         }
         wide_store_t4(a.dz1T[trunk], B, n, b0 + 8 * g + 4 * h, v[0], v[1], v[2], v[3]);
@@ -703,11 +705,11 @@ extern "C" int dm_ppo_wide_dp(int D) { return wide_dp(D); }
 extern "C" int dm_ppo_wide_supported(int B, int D, int H1, int H2, int A) { return wide_supported(B, D, H1, H2, A) ? 1 : 0; }
 
 extern "C" int dm_ppo_wide_grad(const DmPpoWideStep *s, void *stream) {
-  if (!s || !wide_supported(s->B, s->D, s->H1, s->H2, s->A)) return -22;
-  if (!s->obs || !s->act || !s->adv || !s->ret || !s->old_logp || !s->log_std || !s->g_log_std || !s->xbT || !s->part || !s->stats8 || !s->out8) return -22;
+  if (!s || !wide_supported(s->B, s->D, s->H1, s->H2, s->A)) return DM_EINVAL;
+  if (!s->obs || !s->act || !s->adv || !s->ret || !s->old_logp || !s->log_std || !s->g_log_std || !s->xbT || !s->part || !s->stats8 || !s->out8) return DM_EINVAL;
   for (int t = 0; t < 2; t++) {
-    if (!s->wpk[t] || !s->h1T[t] || !s->dz1T[t] || !s->h2T[t] || !s->dz2T[t] || !s->dz3T[t]) return -22;
-    for (int l = 0; l < 3; l++) if (!s->W[t][l] || !s->b[t][l] || !s->gW[t][l] || !s->gb[t][l]) return -22;
+    if (!s->wpk[t] || !s->h1T[t] || !s->dz1T[t] || !s->h2T[t] || !s->dz2T[t] || !s->dz3T[t]) return DM_EINVAL;
+    for (int l = 0; l < 3; l++) if (!s->W[t][l] || !s->b[t][l] || !s->gW[t][l] || !s->gb[t][l]) return DM_EINVAL;
   }
   hipStream_t st = (hipStream_t)stream;
   static int lds_set_for = -1;
@@ -715,8 +717,8 @@ extern "C" int dm_ppo_wide_grad(const DmPpoWideStep *s, void *stream) {
   int dev = 0;
   hipGetDevice(&dev);
   if (lds_set_for != dev) {   // (per device: ADVICE r1)
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(wide_fwdbwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return -5;
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(wide_wgrad_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, WIDE_WG_WAVES * 4 * 4096) != hipSuccess) return -5;
+    if (hipFuncSetAttribute(reinterpret_cast<const void *>(wide_fwdbwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return DM_EHIP;
+    if (hipFuncSetAttribute(reinterpret_cast<const void *>(wide_wgrad_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, WIDE_WG_WAVES * 4 * 4096) != hipSuccess) return DM_EHIP;
     lds_set_for = dev;
   }
   const int Dp = wide_dp(s->D);
@@ -769,5 +771,5 @@ extern "C" int dm_ppo_wide_grad(const DmPpoWideStep *s, void *stream) {
   g.part = s->part; g.nblk = s->B / WIDE_R; g.A = s->A; g.log_std = s->log_std; g.vf_coef = s->vf_coef; g.ent_coef = s->ent_coef; g.stats = s->stats8;
   g.g_log_std = s->g_log_std; g.out8 = s->out8; g.loss_acc = s->loss_acc;
   hipLaunchKernelGGL(wide_wgrad_kernel, dim3(first + 1), dim3(64 * WIDE_WG_WAVES), WIDE_WG_WAVES * 4 * 4096, st, g);
-  return hipGetLastError() == hipSuccess ? 0 : -5;
+  return dm_launch_status();
 }

@@ -14,35 +14,19 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "dm_launch.h"
+#include "dm_rng.h"
+
 namespace {
 
 constexpr int SAC_THREADS = 256;
 constexpr int SAC_EP_HIST = 100;            // SB3's ep_info_buffer: deque(maxlen=100)
 constexpr unsigned SAC_GATHER_TAG = 0xFFFF0000u;
 
-__device__ __forceinline__ unsigned sac_hash32(unsigned long long seed, unsigned a, unsigned b, unsigned c) {
-  unsigned long long x = seed ^ ((unsigned long long)a * 0x9E3779B97F4A7C15ull) ^ ((unsigned long long)b * 0xBF58476D1CE4E5B9ull) ^
-                         ((unsigned long long)c * 0x94D049BB133111EBull);
-  x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull;
-  x ^= x >> 27; x *= 0x94D049BB133111EBull;
-  x ^= x >> 31;
-  return (unsigned)(x >> 32);
-}
-
-// N(0,1) pair (j, j + 1) of row r: Box-Muller exactly as ppo_sample_kernel
-__device__ __forceinline__ void sac_normal2(unsigned long long seed, unsigned r, unsigned ctr, unsigned j, float &e0, float &e1) {
-  const float u1 = ((float)(sac_hash32(seed, r, ctr, j) >> 8) + 1.0f) * (1.0f / 16777216.0f);   // (0, 1]
-  const float u2 = (float)(sac_hash32(seed, r, ctr, j + 1u) >> 8) * (1.0f / 16777216.0f);
-  const float rad = sqrtf(-2.0f * logf(u1));
-  float sn, cs;
-  sincosf(6.283185307179586f * u2, &sn, &cs);
-  e0 = rad * cs;
-  e1 = rad * sn;
-}
-
 __device__ __forceinline__ float sac_clamp_ls(float ls) { return fminf(fmaxf(ls, -20.f), 2.f); }
 
-// fixed-order block sum (256 threads): the same bits on every replay
+// fixed-order block sum (256 threads): the same bits on every replay.  An LDS tree on purpose, not the wave butterfly of
+// ppo_block_sum (dm_ppo_common.h): the two add in different orders, so they are not to be merged.
 __device__ __forceinline__ float sac_block_sum(float v, float *red) {
   red[threadIdx.x] = v;
   __syncthreads();
@@ -64,13 +48,13 @@ __global__ void sac_act_kernel(const float *head, int N, int A, int ld, unsigned
   const unsigned ctr = counter[0];
   for (int j = 0; j < A; j += 2) {
     float eps[2] = {0.f, 0.f};
-    if (!warmup && !deterministic) sac_normal2(seed, (unsigned)e, ctr, (unsigned)j, eps[0], eps[1]);
+    if (!warmup && !deterministic) { const DmNormal2 n = dm_normal2(seed, (unsigned)e, ctr, (unsigned)j); eps[0] = n.e0; eps[1] = n.e1; }
     for (int q = 0; q < 2 && j + q < A; q++) {
       const int c = j + q;
       const float l = lo[c], h = hi[c];
       float a, ae;
       if (warmup) {
-        const float u = (float)(sac_hash32(seed, (unsigned)e, ctr, (unsigned)c) >> 8) * (1.0f / 16777216.0f);   // [0, 1)
+        const float u = (float)(dm_hash32(seed, (unsigned)e, ctr, (unsigned)c) >> 8) * (1.0f / 16777216.0f);   // [0, 1)
         ae = l + u * (h - l);
         a = 2.f * ((ae - l) / (h - l)) - 1.f;
       } else {
@@ -140,7 +124,7 @@ __global__ void sac_gather_kernel(int B, int N, int D, int A, unsigned long long
   const int r = blockIdx.x;
   if (r >= B) return;
   const unsigned long long total = (unsigned long long)ring[1] * (unsigned long long)N;
-  const unsigned h = sac_hash32(seed, (unsigned)r, counter[0], SAC_GATHER_TAG);
+  const unsigned h = dm_hash32(seed, (unsigned)r, counter[0], SAC_GATHER_TAG);
   const size_t i = (size_t)(((unsigned long long)h * total) >> 32);        // < total (total >= 1: the driver learns after a store)
   const int K = D + A;
   for (int c = threadIdx.x; c < D; c += blockDim.x) {
@@ -174,8 +158,8 @@ __global__ void __launch_bounds__(SAC_THREADS) sac_head_fwd_kernel(const float *
     float lp = 0.f;
     float *dst = r < Rpi ? a_pi + (size_t)r * lda : a_next + (size_t)(r - Rpi) * lda;
     for (int j = 0; j < A; j += 2) {
-      float eps[2];
-      sac_normal2(seed, (unsigned)r, ctr, (unsigned)j, eps[0], eps[1]);
+      const DmNormal2 n = dm_normal2(seed, (unsigned)r, ctr, (unsigned)j);
+      const float eps[2] = {n.e0, n.e1};
       for (int q = 0; q < 2 && j + q < A; q++) {
         const int c = j + q;
         const float mu = head[(size_t)r * 2 * A + c], ls = sac_clamp_ls(head[(size_t)r * 2 * A + A + c]);
@@ -258,8 +242,8 @@ __global__ void __launch_bounds__(SAC_THREADS) sac_head_bwd_kernel(const float *
   const float w = st[4] / (float)B;
   for (int r = threadIdx.x; r < B; r += SAC_THREADS) {
     for (int j = 0; j < A; j += 2) {
-      float eps[2];
-      sac_normal2(seed, (unsigned)r, ctr, (unsigned)j, eps[0], eps[1]);
+      const DmNormal2 n = dm_normal2(seed, (unsigned)r, ctr, (unsigned)j);
+      const float eps[2] = {n.e0, n.e1};
       for (int q = 0; q < 2 && j + q < A; q++) {
         const int c = j + q;
         const float mu = head[(size_t)r * 2 * A + c], lsr = head[(size_t)r * 2 * A + A + c], ls = sac_clamp_ls(lsr);
@@ -367,16 +351,14 @@ __global__ void sac_polyak_kernel(const float *p, float *t, long long n, float t
   if (counter && blockIdx.x == 0 && threadIdx.x == 0) counter[0] += 1u;
 }
 
-inline int sac_ok() { return hipGetLastError() == hipSuccess ? 0 : -5; }
-
 }  // namespace
 
 extern "C" int dm_sac_act(const float *head, int N, int A, int ld, unsigned long long seed, const unsigned *counter, int warmup,
                           int deterministic, const float *lo, const float *hi, float *act, float *act_env, void *stream) {
-  if ((!head && !warmup) || !counter || !lo || !hi || !act || !act_env || N < 1 || A < 1 || ld < 2 * A) return -22;
+  if ((!head && !warmup) || !counter || !lo || !hi || !act || !act_env || N < 1 || A < 1 || ld < 2 * A) return DM_EINVAL;
   hipLaunchKernelGGL(sac_act_kernel, dim3((N + 255) / 256), dim3(256), 0, (hipStream_t)stream, head, N, A, ld, seed, counter, warmup,
                      deterministic, lo, hi, act, act_env);
-  return sac_ok();
+  return dm_launch_status();
 }
 
 extern "C" int dm_sac_store(int N, int D, int A, int cap_steps, const float *last_obs, const float *act, const float *rew,
@@ -385,10 +367,10 @@ extern "C" int dm_sac_store(int N, int D, int A, int cap_steps, const float *las
                             float *ep_acc, float *ep_hist, void *stream) {
   if (N < 1 || D < 1 || A < 1 || cap_steps < 1 || !last_obs || !act || !rew || !done || !obs || !terminal_obs || !r_obs || !r_act ||
       !r_rew || !r_done || !r_next || !last_obs_out || !ring || !ep_acc || !ep_hist)
-    return -22;
+    return DM_EINVAL;
   hipLaunchKernelGGL(sac_store_kernel, dim3(N), dim3(64), 0, (hipStream_t)stream, N, D, A, (unsigned)cap_steps, last_obs, act, rew, done,
                      obs, terminal_obs, r_obs, r_act, r_rew, r_done, r_next, last_obs_out, ring, counter, ep_acc, ep_hist);
-  return sac_ok();
+  return dm_launch_status();
 }
 
 extern "C" int dm_sac_gather(int B, int N, int D, int A, unsigned long long seed, const unsigned *counter, const unsigned *ring,
@@ -396,63 +378,63 @@ extern "C" int dm_sac_gather(int B, int N, int D, int A, unsigned long long seed
                              float *obs2, float *xq, float *xpi, float *xt, float *rew, float *done, int *idx_out, void *stream) {
   if (B < 1 || N < 1 || D < 1 || A < 1 || !counter || !ring || !r_obs || !r_act || !r_rew || !r_done || !r_next || !obs2 || !xq ||
       !xpi || !xt || !rew || !done)
-    return -22;
+    return DM_EINVAL;
   hipLaunchKernelGGL(sac_gather_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, B, N, D, A, seed, counter, ring, r_obs, r_act, r_rew,
                      r_done, r_next, obs2, xq, xpi, xt, rew, done, idx_out);
-  return sac_ok();
+  return dm_launch_status();
 }
 
 extern "C" int dm_sac_head_fwd(const float *head, int R, int Rpi, int A, unsigned long long seed, const unsigned *counter, float *a_pi,
                                float *a_next, int lda, float *logp, float *sac_state, int alpha_step, float target_entropy, float lr,
                                void *stream) {
   if (!head || R < 1 || Rpi < 1 || Rpi > R || A < 1 || !counter || !a_pi || (R > Rpi && !a_next) || lda < A || !logp || !sac_state)
-    return -22;
+    return DM_EINVAL;
   hipLaunchKernelGGL(sac_head_fwd_kernel, dim3(1), dim3(SAC_THREADS), 0, (hipStream_t)stream, head, R, Rpi, A, seed, counter, a_pi,
                      a_next, lda, logp, sac_state, alpha_step, target_entropy, lr, 0.9f, 0.999f, 1e-8f);
-  return sac_ok();
+  return dm_launch_status();
 }
 
 extern "C" int dm_sac_critic_loss(const float *q, const float *qt, const float *logp_next, const float *rew, const float *done, int B,
                                   float gamma, float *sac_state, float *dq, float *db3, void *stream) {
-  if (!q || !qt || !logp_next || !rew || !done || B < 1 || !sac_state || !dq) return -22;
+  if (!q || !qt || !logp_next || !rew || !done || B < 1 || !sac_state || !dq) return DM_EINVAL;
   hipLaunchKernelGGL(sac_critic_loss_kernel, dim3(1), dim3(SAC_THREADS), 0, (hipStream_t)stream, q, qt, logp_next, rew, done, B, gamma,
                      sac_state, dq, db3);
-  return sac_ok();
+  return dm_launch_status();
 }
 
 extern "C" int dm_sac_actor_loss(const float *q, const float *logp, int B, float *sac_state, float *dq, void *stream) {
-  if (!q || !logp || B < 1 || !sac_state || !dq) return -22;
+  if (!q || !logp || B < 1 || !sac_state || !dq) return DM_EINVAL;
   hipLaunchKernelGGL(sac_actor_loss_kernel, dim3(1), dim3(SAC_THREADS), 0, (hipStream_t)stream, q, logp, B, sac_state, dq);
-  return sac_ok();
+  return dm_launch_status();
 }
 
 extern "C" int dm_sac_head_bwd(const float *head, int B, int A, unsigned long long seed, const unsigned *counter, const float *dx, int K,
                                int col, const float *sac_state, float *dhead, float *dbias, void *stream) {
-  if (!head || B < 1 || A < 1 || !counter || !dx || col < 0 || col + A > K || !sac_state || !dhead) return -22;
+  if (!head || B < 1 || A < 1 || !counter || !dx || col < 0 || col + A > K || !sac_state || !dhead) return DM_EINVAL;
   hipLaunchKernelGGL(sac_head_bwd_kernel, dim3(1), dim3(SAC_THREADS), 0, (hipStream_t)stream, head, B, A, seed, counter, dx, K, col,
                      sac_state, dhead, dbias);
-  return sac_ok();
+  return dm_launch_status();
 }
 
 extern "C" int dm_sac_linear_relu(const float *X, int ldx, const float *W, const float *bias, float *Y, int B, int O, int I, int nets,
                                   void *stream) {
-  if (!X || !W || !bias || !Y || B < 1 || O < 1 || I < 1 || I > LR_MAXI || ldx < I || nets < 1 || O % nets) return -22;
+  if (!X || !W || !bias || !Y || B < 1 || O < 1 || I < 1 || I > LR_MAXI || ldx < I || nets < 1 || O % nets) return DM_EINVAL;
   const size_t lds = (size_t)(LR_ROWS + LR_COLS) * (I | 1) * sizeof(float);   // <= 49.5 KB at I = 128
   hipLaunchKernelGGL(sac_linear_relu_kernel, dim3((B + LR_ROWS - 1) / LR_ROWS, (O + LR_COLS - 1) / LR_COLS), dim3(256), lds,
                      (hipStream_t)stream, X, ldx, W, bias, Y, B, O, I, O / nets);
-  return sac_ok();
+  return dm_launch_status();
 }
 
 extern "C" int dm_sac_relu_bwd_colsum(const float *dY, const float *Y, float *dZ, float *db, int B, int O, int nets, void *stream) {
-  if (!dY || !Y || !dZ || B < 1 || O < 1 || nets < 1) return -22;
+  if (!dY || !Y || !dZ || B < 1 || O < 1 || nets < 1) return DM_EINVAL;
   hipLaunchKernelGGL(sac_relu_bwd_colsum_kernel, dim3((O + 63) / 64, nets), dim3(256), 0, (hipStream_t)stream, dY, Y, dZ, B, O, db);
-  return sac_ok();
+  return dm_launch_status();
 }
 
 extern "C" int dm_sac_polyak(const float *p, float *t, long long n, float tau, unsigned *counter, void *stream) {
-  if (!p || !t || n < 1) return -22;
+  if (!p || !t || n < 1) return DM_EINVAL;
   long long blocks = (n + 256 * 4 - 1) / (256 * 4);
   if (blocks > 1024) blocks = 1024;
   hipLaunchKernelGGL(sac_polyak_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, t, n, tau, counter);
-  return sac_ok();
+  return dm_launch_status();
 }

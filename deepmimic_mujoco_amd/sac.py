@@ -17,7 +17,6 @@ act + ``env.step_tensor`` + store, the replay ring never leaves HBM.
 from __future__ import annotations
 
 import collections
-import ctypes as C
 import math
 import time
 
@@ -26,9 +25,11 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
+from . import _lib
+from ._lib import ADAM_STATE_FLOATS
+from .rollout import EP_HIST, capture_graph
+
 LOG_SQRT_2PI = 0.5 * math.log(2.0 * math.pi)
-ADAM_STATE_FLOATS = 2 + 1024            # dm_flat_adam_* state2: {scratch, step count, DM_ADAM_PARTIALS partial sums}
-EP_HIST = 100                           # SB3 ep_info_buffer maxlen
 
 
 def actor_layout(D, H1, H2, A):
@@ -185,20 +186,8 @@ class SAC:
         self.stats = {}
 
     # ------------------------------------------------------------------ shared helpers
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
-    @staticmethod
-    def _p(t, off=0):
-        return C.c_void_p(t.data_ptr() + 4 * off) if t is not None else None
-
-    def _L(self):
-        from . import _lib
-        return _lib.load_library()
-
-    def _chk(self, rc, what):
-        if rc != 0:
-            raise RuntimeError("%s failed (%d)" % (what, rc))
+    def _call(self, name, *args):
+        _lib.call(name, *args, device=self.device)
 
     @property
     def alpha(self):
@@ -252,25 +241,21 @@ class SAC:
         return self._rb
 
     def _act_fused(self, obs, warmup, deterministic=False):
-        L, p, s = self._L(), self._p, self._stream()
         rb, P = self._fused_rollout_buffers(), self.policy.actor
         N, A = obs.shape[0], self.act_dim
         if not warmup:
-            self._chk(L.dm_sac_linear_relu(p(obs), self.obs_dim, p(P["W1"]), p(P["b1"]), p(rb["h1"]), N, self.H1, self.obs_dim, 1, s),
-                      "dm_sac_linear_relu")
+            self._call("dm_sac_linear_relu", obs, self.obs_dim, P["W1"], P["b1"], rb["h1"], N, self.H1, self.obs_dim, 1)
             torch.addmm(P["b2"], rb["h1"], P["W2"].t(), out=rb["h2"]).relu_()
             torch.addmm(P["bh"], rb["h2"], P["Wh"].t(), out=rb["head"])
-        self._chk(L.dm_sac_act(None if warmup else p(rb["head"]), N, A, 2 * A, C.c_uint64(self._roll_seed), p(self._roll_ctr),
-                               1 if warmup else 0, 1 if deterministic else 0, p(self.act_lo), p(self.act_hi), p(rb["act"]),
-                               p(rb["act_env"]), s), "dm_sac_act")
+        self._call("dm_sac_act", None if warmup else rb["head"], N, A, 2 * A, self._roll_seed, self._roll_ctr, 1 if warmup else 0,
+                   1 if deterministic else 0, self.act_lo, self.act_hi, rb["act"], rb["act_env"])
         return rb["act"], rb["act_env"]
 
     def _store_fused(self, out):
-        L, p, N, R = self._L(), self._p, self.n_envs, self.ring
-        self._chk(L.dm_sac_store(N, self.obs_dim, self.act_dim, self.cap_steps, p(self._last_obs), p(self._rb["act"]), p(out["rew"]),
-                                 p(out["done"]), p(out["obs"]), p(out["terminal_obs"]), p(R["obs"]), p(R["act"]), p(R["rew"]),
-                                 p(R["done"]), p(R["next_obs"]), p(self._last_obs), p(self.ring_state), p(self._roll_ctr),
-                                 p(self.ep_acc), p(self.ep_hist), self._stream()), "dm_sac_store")
+        N, R = self.n_envs, self.ring
+        self._call("dm_sac_store", N, self.obs_dim, self.act_dim, self.cap_steps, self._last_obs, self._rb["act"], out["rew"], out["done"],
+                   out["obs"], out["terminal_obs"], R["obs"], R["act"], R["rew"], R["done"], R["next_obs"], self._last_obs,
+                   self.ring_state, self._roll_ctr, self.ep_acc, self.ep_hist)
 
     def env_step(self):
         """One vec-env step: act (uniform before learning_starts) + env.step_tensor + store."""
@@ -357,88 +342,75 @@ class SAC:
         return self._fb
 
     def _critic_fwd(self, P, x, h1, h2, q):
-        L, p, B, K = self._L(), self._p, self.batch_size, self.K
-        self._chk(L.dm_sac_linear_relu(p(x), K, p(P["W1"]), p(P["b1"]), p(h1), B, 2 * self.H1, K, 2, self._stream()), "dm_sac_linear_relu")
+        B, K = self.batch_size, self.K
+        self._call("dm_sac_linear_relu", x, K, P["W1"], P["b1"], h1, B, 2 * self.H1, K, 2)
         torch.baddbmm(P["b2"].unsqueeze(1), h1, P["W2"].transpose(1, 2), out=h2).relu_()
         torch.baddbmm(P["b3"].unsqueeze(1), h2, P["W3"].transpose(1, 2), out=q)
 
     def gradient_step_fused(self):
         """One gradient step as a fixed launch sequence (no host read or write): what the captured graph holds."""
-        L, p, s = self._L(), self._p, self._stream()
+        call = self._call
         fb, B, D, A, K, H1, H2 = self._fused_buffers(), self.batch_size, self.obs_dim, self.act_dim, self.K, self.H1, self.H2
-        seed, ctr = C.c_uint64(self._learn_seed), p(self._learn_ctr)
+        seed, ctr, st = self._learn_seed, self._learn_ctr, self.sac_state
         Pa, Pc, Pt = self.policy.actor, self.policy.critic, self.policy.critic_target
         Ga, Gc = arena_views(fb["g_actor"], self._alay), arena_views(fb["g_critic"], self._clay)
         R = self.ring
         # 1. minibatch
-        self._chk(L.dm_sac_gather(B, self.n_envs, D, A, seed, ctr, p(self.ring_state), p(R["obs"]), p(R["act"]), p(R["rew"]),
-                                  p(R["done"]), p(R["next_obs"]), p(fb["obs2"]), p(fb["xq"]), p(fb["xpi"]), p(fb["xt"]), p(fb["rew"]),
-                                  p(fb["done"]), p(fb["idx"]), s), "dm_sac_gather")
+        call("dm_sac_gather", B, self.n_envs, D, A, seed, ctr, self.ring_state, R["obs"], R["act"], R["rew"], R["done"], R["next_obs"],
+             fb["obs2"], fb["xq"], fb["xpi"], fb["xt"], fb["rew"], fb["done"], fb["idx"])
         # 2-4. one actor pass over (obs ; next_obs), squashed heads (a_pi, a'), alpha and its Adam step
-        self._chk(L.dm_sac_linear_relu(p(fb["obs2"]), D, p(Pa["W1"]), p(Pa["b1"]), p(fb["h1a"]), 2 * B, H1, D, 1, s), "dm_sac_linear_relu")
+        call("dm_sac_linear_relu", fb["obs2"], D, Pa["W1"], Pa["b1"], fb["h1a"], 2 * B, H1, D, 1)
         torch.addmm(Pa["b2"], fb["h1a"], Pa["W2"].t(), out=fb["h2a"]).relu_()
         torch.addmm(Pa["bh"], fb["h2a"], Pa["Wh"].t(), out=fb["head"])
-        self._chk(L.dm_sac_head_fwd(p(fb["head"]), 2 * B, B, A, seed, ctr, p(fb["xpi"], D), p(fb["xt"], D), K, p(fb["logp"]),
-                                    p(self.sac_state), 1 if self.ent_auto else 0, C.c_float(self.target_entropy), C.c_float(self.lr), s),
-                  "dm_sac_head_fwd")
+        # a_pi and a' land in the action columns of xpi / xt (row stride K)
+        call("dm_sac_head_fwd", fb["head"], 2 * B, B, A, seed, ctr, fb["xpi"][:, D:], fb["xt"][:, D:], K, fb["logp"], st,
+             1 if self.ent_auto else 0, self.target_entropy, self.lr)
         # 5-6. target and critic loss
         self._critic_fwd(Pt, fb["xt"], fb["h1t"], fb["h2t"], fb["qt"])
         self._critic_fwd(Pc, fb["xq"], fb["h1q"], fb["h2q"], fb["q"])
-        self._chk(L.dm_sac_critic_loss(p(fb["q"]), p(fb["qt"]), p(fb["logp"], B), p(fb["rew"]), p(fb["done"]), B, C.c_float(self.gamma),
-                                       p(self.sac_state), p(fb["dq"]), p(Gc["b3"]), s), "dm_sac_critic_loss")
+        call("dm_sac_critic_loss", fb["q"], fb["qt"], fb["logp"][B:], fb["rew"], fb["done"], B, self.gamma, st, fb["dq"], Gc["b3"])
         dq3 = fb["dq"].view(2, B, 1)
         torch.bmm(dq3.transpose(1, 2), fb["h2q"], out=Gc["W3"])
         torch.bmm(dq3, Pc["W3"], out=fb["dh2"])
-        self._chk(L.dm_sac_relu_bwd_colsum(p(fb["dh2"]), p(fb["h2q"]), p(fb["dh2"]), p(Gc["b2"]), B, H2, 2, s), "dm_sac_relu_bwd_colsum")
+        call("dm_sac_relu_bwd_colsum", fb["dh2"], fb["h2q"], fb["dh2"], Gc["b2"], B, H2, 2)
         torch.bmm(fb["dh2"].transpose(1, 2), fb["h1q"], out=Gc["W2"])
         torch.bmm(fb["dh2"], Pc["W2"], out=fb["dh1"])
-        self._chk(L.dm_sac_relu_bwd_colsum(p(fb["dh1"]), p(fb["h1q"]), p(fb["dh1"]), p(Gc["b1"]), B, H1, 2, s), "dm_sac_relu_bwd_colsum")
+        call("dm_sac_relu_bwd_colsum", fb["dh1"], fb["h1q"], fb["dh1"], Gc["b1"], B, H1, 2)
         torch.bmm(fb["dh1"].transpose(1, 2), fb["xq"].expand(2, B, K), out=Gc["W1"])
         self._adam_fused(self.critic, fb["g_critic"], self.critic_m, self.critic_v, self.critic_s2)
         # 7. actor loss on the stepped critics: input gradients only
         self._critic_fwd(Pc, fb["xpi"], fb["h1p"], fb["h2p"], fb["qp"])
-        self._chk(L.dm_sac_actor_loss(p(fb["qp"]), p(fb["logp"]), B, p(self.sac_state), p(fb["dqp"]), s), "dm_sac_actor_loss")
+        call("dm_sac_actor_loss", fb["qp"], fb["logp"], B, st, fb["dqp"])
         torch.bmm(fb["dqp"].view(2, B, 1), Pc["W3"], out=fb["dh2p"])
-        self._chk(L.dm_sac_relu_bwd_colsum(p(fb["dh2p"]), p(fb["h2p"]), p(fb["dh2p"]), None, B, H2, 2, s), "dm_sac_relu_bwd_colsum")
+        call("dm_sac_relu_bwd_colsum", fb["dh2p"], fb["h2p"], fb["dh2p"], None, B, H2, 2)
         torch.bmm(fb["dh2p"], Pc["W2"], out=fb["dh1p"])
-        self._chk(L.dm_sac_relu_bwd_colsum(p(fb["dh1p"]), p(fb["h1p"]), p(fb["dh1p"]), None, B, H1, 2, s), "dm_sac_relu_bwd_colsum")
+        call("dm_sac_relu_bwd_colsum", fb["dh1p"], fb["h1p"], fb["dh1p"], None, B, H1, 2)
         torch.bmm(fb["dh1p"], Pc["W1"], out=fb["dxp"])
         # 8. squashed-Gaussian backward + actor backward + actor step
-        self._chk(L.dm_sac_head_bwd(p(fb["head"]), B, A, seed, ctr, p(fb["dxp"]), K, D, p(self.sac_state), p(fb["dhead"]), p(Ga["bh"]), s),
-                  "dm_sac_head_bwd")
+        call("dm_sac_head_bwd", fb["head"], B, A, seed, ctr, fb["dxp"], K, D, st, fb["dhead"], Ga["bh"])
         h1a, h2a = fb["h1a"][:B], fb["h2a"][:B]
         torch.mm(fb["dhead"].t(), h2a, out=Ga["Wh"])
         torch.mm(fb["dhead"], Pa["Wh"], out=fb["dh2a"])
-        self._chk(L.dm_sac_relu_bwd_colsum(p(fb["dh2a"]), p(h2a), p(fb["dh2a"]), p(Ga["b2"]), B, H2, 1, s), "dm_sac_relu_bwd_colsum")
+        call("dm_sac_relu_bwd_colsum", fb["dh2a"], h2a, fb["dh2a"], Ga["b2"], B, H2, 1)
         torch.mm(fb["dh2a"].t(), h1a, out=Ga["W2"])
         torch.mm(fb["dh2a"], Pa["W2"], out=fb["dh1a"])
-        self._chk(L.dm_sac_relu_bwd_colsum(p(fb["dh1a"]), p(h1a), p(fb["dh1a"]), p(Ga["b1"]), B, H1, 1, s), "dm_sac_relu_bwd_colsum")
+        call("dm_sac_relu_bwd_colsum", fb["dh1a"], h1a, fb["dh1a"], Ga["b1"], B, H1, 1)
         torch.mm(fb["dh1a"].t(), fb["obs2"][:B], out=Ga["W1"])
         self._adam_fused(self.actor, fb["g_actor"], self.actor_m, self.actor_v, self.actor_s2)
         # 9. Polyak; the learner's draw counter moves on
-        self._chk(L.dm_sac_polyak(p(self.critic), p(self.critic_target), self.critic.numel(), C.c_float(self.tau), ctr, s), "dm_sac_polyak")
+        call("dm_sac_polyak", self.critic, self.critic_target, self.critic.numel(), self.tau, ctr)
 
     def _adam_fused(self, w, g, m, v, s2):
         # max_norm = +inf: the clip coefficient of dm_flat_adam_step is exactly 1 (SB3's SAC does not clip)
-        self._chk(self._L().dm_flat_adam_step(self._p(w), self._p(g), self._p(m), self._p(v), w.numel(), self.lr, 0.9, 0.999, 1e-8,
-                                              float("inf"), 1.0, self._p(s2), ADAM_STATE_FLOATS, self._stream()), "dm_flat_adam_step")
+        self._call("dm_flat_adam_step", w, g, m, v, w.numel(), self.lr, 0.9, 0.999, 1e-8, float("inf"), 1.0, s2, ADAM_STATE_FLOATS)
 
     def _capture(self):
         """Capture gradient_step_fused once.  The warm-up step (library handles, workspaces) runs on a side stream and is undone."""
-        dev = self.device
         snap = [t.clone() for t in self.state_tensors()]
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):
-            self.gradient_step_fused()
-        torch.cuda.current_stream(dev).wait_stream(side)
+        self._graph, _ = capture_graph(self.device, self.gradient_step_fused, warm=self.gradient_step_fused)
         with torch.no_grad():
             for t, s in zip(self.state_tensors(), snap):
                 t.copy_(s)
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            self.gradient_step_fused()
-        self._graph = g
 
     def train(self, gradient_steps):
         for _ in range(gradient_steps):

@@ -1,6 +1,5 @@
 """Per-phase s_memtime stamps of mlp_fwdbwd_kernel, workgroup (0, 0), per wave (diagnostic build:
-hipcc -O3 -fno-slp-vectorize -std=c++17 -fPIC --offload-arch=gfx950 -DMLP_PROFILE -shared
-      -o deepmimic_mujoco_amd/libdeepmimic_hip_mlpprof.so deepmimic_mujoco_amd/csrc/dm_abi.hip)."""
+make -C deepmimic_mujoco_amd/csrc OUT=../libdeepmimic_hip_mlpprof.so EXTRA=-DMLP_PROFILE)."""
 import ctypes as C, os, sys, time
 import numpy as np, torch
 sys.path.insert(0, ".")

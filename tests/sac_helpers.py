@@ -1,9 +1,10 @@
-"""Helpers of the SAC tests (not a conftest): a contextual-bandit tensor env, the counter-based draws of csrc/dm_sac.hip restated
-in numpy, and the conversion between the SAC arenas and the named fp64 state of tests/sac_ref64.py."""
+"""Helpers of the SAC tests (not a conftest): a contextual-bandit tensor env, the uniform and gather draws of csrc/dm_sac.hip on
+the hash of tests/kernel_helpers.py, and the conversion between the SAC arenas and the named fp64 state of tests/sac_ref64.py."""
 import numpy as np
 import torch
 
-M64 = (1 << 64) - 1
+from kernel_helpers import hash32, normals  # noqa: F401 (normals: the pairs of dm_normal2, used by the SAC tests)
+
 GATHER_TAG = 0xFFFF0000
 
 
@@ -52,30 +53,6 @@ class BanditEnv:
 
 
 # ---- csrc/dm_sac.hip draws
-def hash32(seed, a, b, c):
-    x = (seed ^ ((a * 0x9E3779B97F4A7C15) & M64) ^ ((b * 0xBF58476D1CE4E5B9) & M64) ^ ((c * 0x94D049BB133111EB) & M64)) & M64
-    x ^= x >> 30
-    x = (x * 0xBF58476D1CE4E5B9) & M64
-    x ^= x >> 27
-    x = (x * 0x94D049BB133111EB) & M64
-    x ^= x >> 31
-    return x >> 32
-
-
-def normals(seed, rows, ctr, A):
-    """eps [rows x A]: Box-Muller pairs (j, j + 1) of hash(seed, row, ctr, j), as sac_normal2 (float64 of the same uniforms)."""
-    out = np.zeros((rows, A))
-    for r in range(rows):
-        for j in range(0, A, 2):
-            u1 = ((hash32(seed, r, ctr, j) >> 8) + 1.0) / 16777216.0
-            u2 = (hash32(seed, r, ctr, j + 1) >> 8) / 16777216.0
-            rad = np.sqrt(-2.0 * np.log(u1))
-            out[r, j] = rad * np.cos(2 * np.pi * u2)
-            if j + 1 < A:
-                out[r, j + 1] = rad * np.sin(2 * np.pi * u2)
-    return out
-
-
 def uniforms(seed, rows, ctr, A):
     return np.array([[(hash32(seed, r, ctr, j) >> 8) / 16777216.0 for j in range(A)] for r in range(rows)])
 

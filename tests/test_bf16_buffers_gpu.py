@@ -15,12 +15,12 @@ import numpy as np
 import pytest
 import torch
 
+from kernel_helpers import BF16_NAN, DEV, GUARD, lib as _lib, offset as _offset, ptr as _p, stream as _stream
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DEV = torch.device("cuda", 0)
-GUARD = 4096
-QNAN16 = 0x7FC0
+QNAN16 = BF16_NAN
 NAMES = ["walk", "run", "dance_b", "spinkick"]
 BF = torch.bfloat16
 # (N, D, A): humanoid3d at the sizes of configs 3 and 5, G1-shaped rows (85 = G1 DPEnv, 98 = G1 DPCombinedEnv, 90 = neither) with an N
@@ -33,33 +33,12 @@ SPECIAL = [1.99609375 + 2.0 ** -9, -(1.99609375 + 2.0 ** -9), 1.0 + 2.0 ** -8, 1
            -99.70703125, 63.75 + 0.125, 3.0e-39, 0.333251953125, -7.00390625]
 
 
-def _p(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream(DEV).cuda_stream)
-
-
-def _lib():
-    from deepmimic_mujoco_amd import _lib as L
-    return L.load_library()
-
-
 def _bits(t):
     return t.view(torch.int16) if t.dtype == BF else t.view(torch.int32)
 
 
 def _same(a, b):
     return a.dtype == b.dtype and a.shape == b.shape and torch.equal(_bits(a.contiguous()), _bits(b.contiguous()))
-
-
-def _offset(t, off):
-    """The same values as a view that starts `off` elements into a larger buffer."""
-    buf = torch.zeros(t.numel() + off + 7, dtype=t.dtype, device=DEV)
-    v = buf[off:off + t.numel()].view(t.shape)
-    v.copy_(t)
-    return v
 
 
 class Out:

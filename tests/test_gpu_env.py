@@ -3,17 +3,9 @@ auto-reset semantics, multi-clip batches, free-running rollouts and a short PPO 
 import numpy as np
 import pytest
 
+from kernel_helpers import hash32 as _hash32, ptr as _ptr, stream as _stream
+
 pytestmark = pytest.mark.gpu
-
-
-def _hash32(seed, env, step, j):
-    M = (1 << 64) - 1
-    seed, env, step, j = int(seed), int(env), int(step), int(j)
-    x = (seed ^ (env * 0x9E3779B97F4A7C15) ^ (step * 0xBF58476D1CE4E5B9) ^ (j * 0x94D049BB133111EB)) & M
-    x ^= x >> 30; x = (x * 0xBF58476D1CE4E5B9) & M
-    x ^= x >> 27; x = (x * 0x94D049BB133111EB) & M
-    x ^= x >> 31
-    return x >> 32
 
 
 def test_dpenv_surface_matches_oracle(model, clips, oracle_clips):
@@ -442,8 +434,7 @@ def test_fused_tanh_layer_kernels_match_torch():
     from deepmimic_mujoco_amd import _lib
     L = _lib.load_library()
     dev = torch.device("cuda", 0)
-    p = lambda t: C.c_void_p(t.data_ptr())
-    st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    p, st = _ptr, _stream(dev)
     g = torch.Generator(device="cpu").manual_seed(3)
     for B, O, I in ((4096, 1024, 67), (2048, 1024, 72), (1024, 512, 85), (4096, 1024, 98), (1024, 300, 128), (1000, 77, 5)):
         x = torch.randn(B, I, generator=g).to(dev)
@@ -536,8 +527,7 @@ def test_flat_adam_abi_checks_state2_and_loads_r2_checkpoints(tmp_path):
     n = 1000
     p_, g_, m_, v_ = (torch.zeros(n, device=dev) for _ in range(4))
     st = torch.zeros(2, device=dev)
-    vp = lambda t: C.c_void_p(t.data_ptr())
-    s0 = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    vp, s0 = _ptr, _stream(dev)
     assert L.dm_flat_adam_step(vp(p_), vp(g_), vp(m_), vp(v_), n, 1e-3, 0.9, 0.999, 1e-5, 0.5, 1.0, vp(st), 2, s0) == -22
     assert L.dm_flat_adam_step(vp(p_), vp(g_), vp(m_), vp(v_), n, 1e-3, 0.9, 0.999, 1e-5, 0.5, 0.0, vp(st), 2 + 1024, s0) == -22
     env = HipDeepMimicVecEnv(32, motion="walk", seed=1)
@@ -680,9 +670,9 @@ def test_policy_forward_kernel_matches_torch(arch, N, D):
     # same draws as the two-kernel path: counter[0] + draw_offset = 8
     a2, e2, l2 = z(N, 28), z(N, 28), z(N)
     ctr8 = torch.tensor([8], dtype=torch.int32, device=dev)
-    p = lambda t: C.c_void_p(t.data_ptr())
+    p = _ptr
     rc = _lib.load_library().dm_policy_sample(p(mean), p(pol.log_std), N, 28, C.c_uint64(1234), p(ctr8), p(lo), p(hi), p(a2), p(e2), p(l2),
-                                              C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+                                              _stream(dev))
     assert rc == 0
     assert torch.allclose(a2, act, atol=1e-6) and torch.allclose(l2, logp, atol=3e-4)
     # deterministic head: act = mean

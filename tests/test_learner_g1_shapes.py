@@ -15,42 +15,17 @@ import torch
 import torch.nn as nn
 
 import ppo_ref64 as R
+from kernel_helpers import DEV, GUARD, normals  # noqa: F401
+from kernel_helpers import check_out8 as _check_out8, guard_ok as _guard_ok, guarded as _guarded, lib as _lib, note as _note, ptr as _p, stream as _stream
 
 pytestmark = pytest.mark.gpu
 
 A = 23
-DEV = torch.device("cuda", 0)
-GUARD = 4096           # NaN floats behind the last row of every output: a stray write shows up there
 
 
-def _lib():
-    from deepmimic_mujoco_amd import _lib as L
-    return L.load_library()
-
-
-def _p(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream(DEV).cuda_stream)
-
-
-def _guarded(*shape):
-    """(buffer, view): a NaN-filled buffer and a contiguous view of `shape` at its start, GUARD floats of NaN behind it."""
-    n = int(np.prod(shape))
-    buf = torch.full((n + GUARD,), float("nan"), device=DEV)
-    return buf, buf[:n].view(*shape)
-
-
-def _note(what, err, tol):
-    """The measured error against its bound (printed with pytest -s: the numbers the docstrings quote)."""
-    print("measured %-34s %10.3g   bound %10.3g   margin %8.1fx" % (what, err, tol, tol / max(err, 1e-30)))
-    return err
-
-
-def _guard_ok(buf, view):
-    return bool(torch.isnan(buf[view.numel():]).all())
+def _eps64(seed, ctr, N):
+    """fp64 draws [N, A] of (seed, env, counter, action index); the last pair of the odd A half used."""
+    return torch.tensor(normals(seed, N, ctr, A), device=DEV)
 
 
 def _g1_bounds():
@@ -67,30 +42,6 @@ def _asym_bounds():
     lo[5], hi[5] = 0.3, 1.7
     lo[17], hi[17] = -2.2, -0.4
     return lo, hi
-
-
-def _hash32(seed, e, ctr, j):
-    """The kernels' counter-based hash (numpy uint64, wrapping), vectorised over e and j."""
-    M64 = np.uint64(0xFFFFFFFFFFFFFFFF)
-    with np.errstate(over="ignore"):
-        x = (np.uint64(seed) ^ (e.astype(np.uint64) * np.uint64(0x9E3779B97F4A7C15)) ^ (np.uint64(ctr) * np.uint64(0xBF58476D1CE4E5B9))
-             ^ (j.astype(np.uint64) * np.uint64(0x94D049BB133111EB))) & M64
-        x ^= x >> np.uint64(30); x *= np.uint64(0xBF58476D1CE4E5B9)
-        x ^= x >> np.uint64(27); x *= np.uint64(0x94D049BB133111EB)
-        x ^= x >> np.uint64(31)
-    return (x >> np.uint64(32)).astype(np.uint64)
-
-
-def _eps64(seed, ctr, N):
-    """fp64 Box-Muller draws [N, A] of (seed, env, counter, action index): pair (j, j + 1) from hashes j and j + 1, the last pair
-    of an odd A half used."""
-    e = np.arange(N)[:, None]
-    j = np.arange(0, A + 1, 2)[None, :]
-    u1 = ((_hash32(seed, e, ctr, j) >> np.uint64(8)).astype(np.float64) + 1.0) / 16777216.0
-    u2 = (_hash32(seed, e, ctr, j + 1) >> np.uint64(8)).astype(np.float64) / 16777216.0
-    rad = np.sqrt(-2.0 * np.log(u1))
-    eps = np.stack([rad * np.cos(2 * np.pi * u2), rad * np.sin(2 * np.pi * u2)], -1).reshape(N, -1)[:, :A]
-    return torch.tensor(eps, device=DEV)
 
 
 def _policy(D, arch, seed, bounds=None):
@@ -255,18 +206,6 @@ def _minibatch(pol, D, B, seed):
         adv = torch.randn(B, device=DEV, generator=g) * 2 + 0.3
         ret = torch.randn(B, device=DEV, generator=g)
     return obs, act, adv, ret, old_logp
-
-
-def _check_out8(out8, ref8, ratio64, clip, B):
-    """loss terms within 2e-5 x max(1, |ref|) (the A = 28 loss bound), approx_kl within 5e-5, the advantage statistics within
-    1e-5 relative, the clip fraction exact up to the samples whose fp64 ratio lies within 1e-3 of the clip boundary."""
-    o, r = [float(x) for x in out8], [float(x) for x in ref8]
-    for k in (0, 1, 2, 3):
-        assert _note("out8[%d]" % k, abs(o[k] - r[k]), 2e-5 * max(1.0, abs(r[k]))) < 2e-5 * max(1.0, abs(r[k])), (k, o[k], r[k])
-    assert _note("out8[4] approx_kl", abs(o[4] - r[4]), 5e-5) < 5e-5, (o[4], r[4])
-    amb = int((((ratio64 - 1).abs() - clip).abs() < 1e-3).sum())
-    assert abs(o[5] - r[5]) <= amb / B + 1e-6, (o[5], r[5], amb)
-    assert abs(o[6] - r[6]) < 1e-5 * max(1.0, abs(r[6])) and abs(o[7] - r[7]) < 1e-5 * abs(r[7])
 
 
 @pytest.mark.parametrize("D,B,normalize,ent", [(98, 4096, True, 0.0), (98, 4096, False, 0.01), (98, 4096, True, 0.01), (98, 4096, False, 0.0),

@@ -29,12 +29,11 @@ import torch.nn as nn
 
 import ppo_ref64 as R
 import ppo_wide_ref64 as W
+from kernel_helpers import BF16_NAN, DEV, GUARD  # noqa: F401
+from kernel_helpers import check_out8, guard_ok as _guard_ok, guard_ok_bf16 as _guard_ok_bf16, guarded as _guarded, guarded_bf16 as _guarded_bf16, lib as _lib, note, stream as _stream
 
 pytestmark = pytest.mark.gpu
 
-DEV = torch.device("cuda", 0)
-GUARD = 4096             # NaN floats / 0x7FC0 bf16 behind every array: a stray write shows up there
-BF16_NAN = 0x7FC0
 KEYS = list(W.SHAPES)
 MAX_DIFFERING = 0.05     # at most this fraction of a stage's elements may differ at all from the reference's bf16 value
 STAGES = ("h1", "h2", "dz3", "dz2", "dz1")
@@ -45,39 +44,8 @@ def _L():
     return L
 
 
-def _lib():
-    return _L().load_library()
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream(DEV).cuda_stream)
-
-
-def _note(what, err, tol):
-    """The measured error against its bound (printed with pytest -s: the numbers the docstrings quote)."""
-    print("measured %-46s %10.3g   bound %10.3g   margin %8.1fx" % (what, err, tol, tol / max(err, 1e-30)))
-    return err
-
-
-def _guarded(n, fill=float("nan")):
-    """(buffer, view): an fp32 buffer and the view of its first n floats; GUARD floats of NaN behind the view."""
-    buf = torch.full((n + GUARD,), float("nan"), device=DEV)
-    buf[:n] = fill
-    return buf, buf[:n]
-
-
-def _guard_ok(buf, view):
-    return bool(torch.isnan(buf[view.numel():]).all())
-
-
-def _guarded_bf16(n):
-    """(buffer, view) of bf16 scratch as int16, every element 0x7FC0 (a bf16 NaN), GUARD elements behind the view."""
-    buf = torch.full((n + GUARD,), BF16_NAN, dtype=torch.int16, device=DEV)
-    return buf, buf[:n]
-
-
-def _guard_ok_bf16(buf, view):
-    return bool((buf[view.numel():] == BF16_NAN).all())
+_note = functools.partial(note, width=46)
+_check_out8 = functools.partial(check_out8, width=46)
 
 
 def _policy(arch, D, A, seed=13):
@@ -308,18 +276,6 @@ def test_wide_gradients_match_the_mirrored_reference(key):
 
 
 # ------------------------------------------------------------------------------------------------ 4. out8, 5. folds, 6. guards
-def _check_out8(out8, ref8, ratio64, clip, B):
-    """(as in test_learner_g1_shapes.py) loss terms within 2e-5 x max(1, |ref|), approx_kl within 5e-5, the advantage statistics
-    within 1e-5 relative, the clip fraction exact up to the samples whose fp64 ratio lies within 1e-3 of the clip boundary."""
-    o, r = [float(x) for x in out8], [float(x) for x in ref8]
-    for k in (0, 1, 2, 3):
-        assert _note("out8[%d]" % k, abs(o[k] - r[k]), 2e-5 * max(1.0, abs(r[k]))) < 2e-5 * max(1.0, abs(r[k])), (k, o[k], r[k])
-    assert _note("out8[4] approx_kl", abs(o[4] - r[4]), 5e-5) < 5e-5, (o[4], r[4])
-    amb = int((((ratio64 - 1).abs() - clip).abs() < 1e-3).sum())
-    assert abs(o[5] - r[5]) <= amb / B + 1e-6, (o[5], r[5], amb)
-    assert abs(o[6] - r[6]) < 1e-5 * max(1.0, abs(r[6])) and abs(o[7] - r[7]) < 1e-5 * abs(r[7])
-
-
 @pytest.mark.parametrize("key", KEYS)
 def test_wide_out8_folds_and_guards(key):
     """All eight out8 entries by _check_out8's rules against the MIRRORED reference's out8 (loss terms 2e-5, approx_kl 5e-5, clip

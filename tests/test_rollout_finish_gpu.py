@@ -9,31 +9,13 @@ import pytest
 import torch
 
 import monitor_ref as M
+from kernel_helpers import DEV, GUARD, guarded as _guarded, offset as _offset, ptr as _p  # noqa: F401
 from sac_helpers import BanditEnv
 
 pytestmark = pytest.mark.gpu
 
-DEV = torch.device("cuda", 0)
-GUARD = 4096
 HIST = 100
 GAMMA, LAM = 0.99, 0.95
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr())
-
-
-def _offset(t, off):
-    """The same values as a view that starts `off` elements into a larger buffer."""
-    buf = torch.zeros(t.numel() + off + 7, dtype=t.dtype, device=DEV)
-    v = buf[off:off + t.numel()].view(t.shape)
-    v.copy_(t)
-    return v
-
-
-def _guarded(n, shape=None):
-    buf = torch.full((n + GUARD,), float("nan"), device=DEV)
-    return buf, buf[:n].view(*(shape or (n,)))
 
 
 class Finish:
@@ -42,8 +24,8 @@ class Finish:
     def __init__(self, T, N):
         from deepmimic_mujoco_amd import _lib
         self.L, self.T, self.N = _lib.load_library(), T, N
-        self.adv_b, self.adv = _guarded(T * N, (T, N))
-        self.ret_b, self.ret = _guarded(T * N, (T, N))
+        self.adv_b, self.adv = _guarded(T, N)
+        self.ret_b, self.ret = _guarded(T, N)
         self.acc_b, self.acc = _guarded(2 * N)
         self.hist_b, self.hist = _guarded(2 * HIST)
         self.stats_b, st = _guarded(16)

@@ -195,3 +195,18 @@ def test_fused_sac_learns_the_bandit():
     rnd = float(env.reward(obs, torch.rand(512, 2, device="cuda") * 4 - 2).mean())
     assert sac._graph is not None and sac._n_updates > 600
     assert r > -0.05 and rnd < -1.0, (r, rnd)
+
+
+def test_rejected_sac_call_names_its_entry_point():
+    """What the SAC driver's calls go through: dm_sac_linear_relu refuses I = 129 (one over its 128-column LDS tile) on the host,
+    `_lib.call` raises with the entry point's name and -22, and nothing was launched: the output keeps its fill.  B = 2, O = 4 is
+    the smallest argument set the entry point rejects."""
+    from deepmimic_mujoco_amd import _lib
+    DEV = torch.device("cuda", 0)
+    B, O, I = 2, 4, 129
+    x, w, b = torch.ones(B, I, device=DEV), torch.ones(O, I, device=DEV), torch.ones(O, device=DEV)
+    y = torch.full((B, O), -7.0, device=DEV)
+    with pytest.raises(RuntimeError, match=r"^dm_sac_linear_relu failed \(-22\)$"):
+        _lib.call("dm_sac_linear_relu", x, I, w, b, y, B, O, I, 1, device=DEV)
+    torch.cuda.synchronize(DEV)
+    assert bool((y == -7.0).all())
