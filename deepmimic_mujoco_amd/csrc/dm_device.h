@@ -96,7 +96,7 @@ struct EnvLds {
   unsigned long long prof_t, prof_t0; unsigned prof[16], prof_stage[4];  // diagnostic stamps (-DDM_PROFILE build only)
 #endif
   int32_t info[8];                    // ncon, nefc, nlimit, solver_iter, overflow (last forward evaluation)
-  int16_t rowinfo[DMK_MAXROW];        // contact rows: (contact << 3) | edge | 0x4000 (whole pyramid kept); limit rows: -(2 dof + side + 1)
+  int16_t rowinfo[DMK_MAXROW];        // contact rows: (contact << 3) | edge; limit rows: -(2 dof + side + 1)
   // velocity-stage scratch (dead before the constraint stage) / box-box polygon scratch
   union {
     struct {

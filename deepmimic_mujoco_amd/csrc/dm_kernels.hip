@@ -1139,7 +1139,7 @@ template <bool MF>   // MF: all rows live in lanes 0..31 (nefc <= 32): the dof-b
 __device__ __forceinline__ void build_row(GDev &T, EnvLds &S, const int r, const int nefc, const float (&com)[3],
                                           float (&J)[DMK_NV], float &R, float &Dd, float &aref, float &bb, float &jw) {
       float rpos = 0, rmargin = 0, rdiag = 1, mu = 0;
-      int rtype = -1, full = 0;
+      int rtype = -1;
       float wl[3] = {0, 0, 0}, wa[3] = {0, 0, 0};
       unsigned long long cm1 = 0, cm2 = 0;
       int ldof = -1;
@@ -1157,7 +1157,6 @@ __device__ __forceinline__ void build_row(GDev &T, EnvLds &S, const int r, const
           rdiag = T.d_invw[ldof];
         } else {
           int ci = (info >> 3) & 0x3F, e = info & 7;
-          full = (info & 0x4000) ? 1 : 0;
           int g1 = S.c_g1[ci], g2 = S.c_g2[ci];
           int b1 = T.g_body[g1], b2 = T.g_body[g2];
           int cd1 = T.g_condim[g1], cd2 = T.g_condim[g2];
@@ -1232,7 +1231,7 @@ __device__ __forceinline__ void build_row(GDev &T, EnvLds &S, const int r, const
         float sol[5] = {T.solimp[0], T.solimp[1], T.solimp[2], T.solimp[3], T.solimp[4]};
         float imp = impedance(sol, rpos, rmargin);
         R = fmaxf(MINVALF, (1 - imp) * rdiag / imp);
-        if (rtype == 2 && full) R = 2 * mu * mu * R;
+        if (rtype == 2) R = 2 * mu * mu * R;
         aref = -T.B * vel - T.K * imp * (rpos - rmargin);
         bb = jqs - aref;
         Dd = 1.0f / R;
@@ -1389,12 +1388,19 @@ __device__ __forceinline__ float fwd_constraint(GDev &T, const int lane, const i
       unsigned long long m1 = __ballot(have && !dim3), m4 = __ballot(have && dim3);
       int roff = nlimit + __popcll(m1 & lt) + 4 * __popcll(m4 & lt);
       int rtot = nlimit + __popcll(m1) + 4 * __popcll(m4);
-      if (have) {
-        int nr = dim3 ? 4 : 1;
-        for (int e = 0; e < nr; e++)
-          if (roff + e < DMK_MAXROW) S.rowinfo[roff + e] = (int16_t)((lane << 3) | e | (((roff + nr) <= DMK_MAXROW) ? 0x4000 : 0));
+      const int nr = dim3 ? 4 : 1;
+      // the row cap, as mj_addConstraint / mj_instantiateContact apply njmax: a contact's rows go in as one block or not at
+      // all, and the first contact that does not fit ends the list (no later contact gets rows, no pyramid is kept in part)
+      if (rtot > DMK_MAXROW) {
+        const unsigned long long nofit = __ballot(have && roff + nr > DMK_MAXROW);
+        const int first = __ffsll((long long)nofit) - 1;
+        overflow |= 2;
+        rtot = __builtin_amdgcn_readlane(roff, first);
+        have = have && lane < first;
       }
-      if (rtot > DMK_MAXROW) { overflow |= 2; rtot = DMK_MAXROW; }
+      if (have) {
+        for (int e = 0; e < nr; e++) S.rowinfo[roff + e] = (int16_t)((lane << 3) | e);
+      }
       nefc = rtot;
     }
     SYNC();

@@ -156,10 +156,19 @@ int dm_set_seed(DmHandle h, uint64_t seed);
 
 /* Derived quantities of the LAST forward evaluation of every env, for parity tests:
  * sim.data.body_xpos/geom_xpos/cvel/qacc and the contact list.  Layout per env (floats):
- *   [0:42) xpos 14x3 | [42:90) geom_xpos 16x3 | [90:174) cvel 14x6 | [174:208) qacc |
- *   [208:242) qacc_smooth | 242 ncon | 243 nefc | 244 solver_iter | 245 nlimit | 246 overflow |
- *   247/248 per-RK-stage ncon / nefc packed one byte per stage (int32 bit pattern) |
- *   [256:256+3*32) contacts: (geom1, geom2, dist) x 32 | [352:416) efc_force
+ *   [0:42) xpos 14x3 | [42:90) geom_xpos 16x3 | [90:174) cvel 14x6 | [174:208) qacc | [208:242) qacc_smooth
+ * Read by tests/test_gpu_parity.py, tests/test_gpu_env.py (xpos, qacc) and tests/test_constraint_paths_gpu.py; the scalar slots:
+ *   242 ncon          contacts kept (<= 32, in canonical pair order)
+ *   243 nefc          constraint rows (<= 128): limit rows in joint order, then the rows of each contact
+ *   244 solver_iter   PGS sweeps run (0 without rows, at most DmModel.iterations)
+ *   245 nlimit        joint-limit rows among them
+ *   246 overflow      bit 0: more than 32 contacts were found, the first 32 are kept; bit 1: the rows did not fit into 128, the
+ *                     first contact whose rows do not all fit and every later one got none (no pyramid is kept in part)
+ *   247, 248          ncon / nefc of the four RK stages of the last step, one byte per stage (int32 bit pattern)
+ *   [249:256)         unused
+ *   [256:352)         the contacts, (geom1, geom2, dist) x 32; unused slots hold (-1, -1, 0)
+ *   [352:416)         efc_force of rows 0..63 as the last evaluation with 1..64 rows left it (0 from row nefc on); the wide path
+ *                     (65..128 rows) and an evaluation without rows do not write here.  A DM_PROFILE build overwrites [352:372).
  * => DM_DEBUG_STRIDE floats per env. Enabled by dm_set_debug(h, buf) with buf float[N*stride] or NULL. */
 #define DM_DEBUG_STRIDE 416
 int dm_set_debug(DmHandle h, float *debug_buf);

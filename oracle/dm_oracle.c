@@ -859,6 +859,18 @@ static void make_constraint(const DmModel *m, DmoData *d) { /* [EXT] mj_makeCons
     DmoContact *c = &d->contact[ci];
     int b1 = m->geom_body[c->geom1], b2 = m->geom_body[c->geom2];
     c->efc_address = d->nefc;
+    { /* [EXT] mj_addConstraint takes the rows of one contact as a block: when they do not all fit (nefc + size > njmax)
+       * none of them is added, and mj_instantiateContact stops there, so no later contact gets rows either.  A friction
+       * pyramid is never kept in part. */
+      int size = c->dim == 1 ? 1 : 2 * (c->dim - 1);
+      if (d->nefc + size > d->maxrow) {
+        for (int cj = ci; cj < d->ncon; cj++) {
+          d->contact[cj].efc_address = d->nefc;
+          d->overflow_row += d->contact[cj].dim == 1 ? 1 : 2 * (d->contact[cj].dim - 1);
+        }
+        break;
+      }
+    }
     jac_point(m, d, j1, c->pos, b1);
     jac_point(m, d, j2, c->pos, b2);
     for (int i = 0; i < 3 * NV; i++) jd[i] = j2[i] - j1[i];
@@ -902,7 +914,7 @@ static void make_constraint(const DmModel *m, DmoData *d) { /* [EXT] mj_makeCons
     DmoContact *c = &d->contact[ci];
     if (c->dim <= 1) continue;
     int a = c->efc_address, n = 2 * (c->dim - 1);
-    if (a + n > d->nefc) continue; /* dropped by the row cap */
+    if (a + n > d->nefc) continue; /* got no rows: the row cap */
     double Rpy = TW.redge * c->mu * c->mu * d->efc_R[a];
     for (int k = 0; k < n; k++) d->efc_R[a + k] = Rpy;
   }

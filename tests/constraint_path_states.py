@@ -1,0 +1,323 @@
+"""Seeded searches, by the fp64 oracle alone, for states that put the constraint stage on each of its paths.
+
+humanoid3d (caps 32 contacts / 128 rows, `humanoid_states`): the row-count paths of dm_step_kernel (0, 1..7 scalar, 8..32 matrix
+pipe, 33..64 streamed columns, 65..128 two rows per lane) with their boundaries, both caps, both transposes of the force tail
+(more / at most 20 rows carrying force), warm start kept / discarded, PGS leaving early / at `iterations`, every limited joint
+beyond either bound.  Unitree G1 (caps 48 / 256, `g1_states`): getup frames pressed into the floor, cut by the contact cap, with
+uncut controls of 40..48 contacts.
+
+Every state is rounded to fp32 before the oracle sees it, so the engine under test gets the same inputs.  Draws near an
+activation tie are dropped: a contact with |dist - margin| < 2e-5, a limited joint within 1e-5 rad of a bound.  Plain helper: no
+GPU, no test in here; tests/test_constraint_paths_cpu.py asserts the quotas, tests/test_constraint_paths_gpu.py runs the states.
+"""
+import numpy as np
+
+MAXCON, MAXROW = 32, 128            # DMK_MAXCON, DMK_MAXROW (csrc/dm_kernels.hip)
+G1_MAXCON, G1_MAXROW = 48, 256      # MAXCON, MAXROW (csrc/dm_g1.hip)
+TIE_DIST, TIE_LIMIT = 2e-5, 1e-5
+BOUNDARY_NEFC = (0, 1, 7, 8, 9, 31, 32, 33, 63, 64, 65)
+TOP_NEFC = (127, 128)
+INTERIORS = ((1, 7), (8, 32), (33, 64), (65, 128))     # open intervals: strictly between the two ends
+
+_CACHE = {}
+
+
+def _f32(x):
+    return np.asarray(x, np.float64).astype(np.float32).astype(np.float64)
+
+
+class _Probe:
+    """One oracle environment; evaluate() labels a (qpos, qvel, qacc_warmstart)."""
+
+    def __init__(self, model):
+        from oracle.oracle import OracleSim
+        self.model = model
+        self.sim = OracleSim(model)
+        self.sim.set_caps(MAXCON, MAXROW)
+        self.lo, self.hi = model.jnt_range[1:, 0].copy(), model.jnt_range[1:, 1].copy()
+
+    def forward(self, q, v, w):
+        """-> (error, contact-cap counter delta, row-cap counter delta): the oracle's two counters accumulate, so differences."""
+        s = self.sim
+        oc, orow = s.geti("overflow_con"), s.geti("overflow_row")
+        s.set("ctrl", np.zeros(28))
+        s.set("qacc_warmstart", w)
+        err = s.set_state(q, v)
+        return err, s.geti("overflow_con") - oc, s.geti("overflow_row") - orow
+
+    def evaluate(self, q, v, w):
+        s = self.sim
+        err, dcon, drow = self.forward(q, v, w)
+        if err != 0:
+            return None
+        con = s.get("contact")
+        if len(con) and np.any(np.abs(con[:, 0] - 0.001) < TIE_DIST):
+            return None
+        ang = q[7:]
+        if np.any(np.abs(ang - self.lo) < TIE_LIMIT) or np.any(np.abs(ang - self.hi) < TIE_LIMIT):
+            return None
+        nefc, nlimit = s.nefc, s.geti("nlimit")
+        lab = dict(nefc=nefc, ncon=len(con), nlimit=nlimit, cut_con=dcon > 0, cut_row=drow > 0, sweeps=s.geti("solver_iter"),
+                   low=tuple(np.nonzero(ang < self.lo)[0]), high=tuple(np.nonzero(ang > self.hi)[0]),
+                   warm_nonzero=bool(np.any(w != 0)), straddle=False, nact=0, warm=None)
+        if nefc:
+            # rows per contact: a pyramid (4) where either geom has condim 3, else one frictionless row
+            # (the first contact whose rows do not all fit gets none, nor does any later one: "straddle" when it is a pyramid
+            # that would have crossed row 128, which leaves nefc at 125..127)
+            addr = nlimit
+            for c in con:
+                nr = 4 if int(c[15]) >= 3 else 1
+                if addr + nr > MAXROW:
+                    lab["straddle"] = addr < MAXROW
+                    break
+                addr += nr
+            lab["nact"] = int((s.get("efc_force") > 0).sum())
+            # mj_fwdConstraint's warm-start rule, restated from the exported rows: forces implied by qacc_warmstart, kept unless
+            # their dual cost is positive
+            J, aref, D, AR, b = s.get("efc_J"), s.get("efc_aref"), s.get("efc_D"), s.get("efc_AR"), s.get("efc_b")
+            jar = J @ w - aref
+            f = np.where(jar < 0, -D * jar, 0.0)
+            terms = f * (0.5 * (AR @ f) + b)
+            cost = terms.sum()
+            if not np.any(f):
+                lab["warm"] = None                      # no force implied: both branches start from zero
+            elif abs(cost) < 1e-4 * np.abs(terms).sum():
+                return None                             # the sign of the cost is an fp32 coin toss: a tie like the others
+            else:
+                lab["warm"] = "discarded" if cost > 0 else "kept"
+        return lab
+
+    def reference(self):
+        """What the GPU tests compare with, of the evaluation just made: the contact list, both accelerations and, up to 64
+        rows, the row Jacobian, the row forces and the dense mass matrix (MuJoCo's qM: dof i, then its ancestors)."""
+        s, m = self.sim, self.model
+        ref = dict(contact=s.get("contact").copy(), qacc=s.get("qacc").copy(), qacc_smooth=s.get("qacc_smooth").copy())
+        if 0 < s.nefc <= 64:
+            qM, M = s.get("qM"), np.zeros((34, 34))
+            for i in range(34):
+                adr, j = int(m.dof_Madr[i]), i
+                while j >= 0:
+                    M[i, j] = M[j, i] = qM[adr]
+                    adr, j = adr + 1, int(m.dof_parent[j])
+            ref.update(J=s.get("efc_J").copy(), force=s.get("efc_force").copy(), M=M)
+        return ref
+
+    def stable_sweeps(self, q, v, w, sweeps):
+        """True when the oracle's sweep count stays put with its tolerance scaled by 0.9 and by 1.1."""
+        cm = self.model.cstruct
+        tol = cm.tolerance
+        try:
+            for k in (0.9, 1.1):
+                cm.tolerance = tol * k
+                err, _, _ = self.forward(q, v, w)
+                if err != 0 or self.sim.geti("solver_iter") != sweeps:
+                    return False
+        finally:
+            cm.tolerance = tol
+        return True
+
+
+def _humanoid_quotas():
+    """name -> [predicate(label), states wanted]"""
+    Q = {}
+    for n in BOUNDARY_NEFC:
+        Q["nefc == %d" % n] = [lambda L, n=n: L["nefc"] == n and not (L["cut_con"] or L["cut_row"]), 4]
+    for n in TOP_NEFC:
+        Q["nefc == %d uncut" % n] = [lambda L, n=n: L["nefc"] == n and not (L["cut_con"] or L["cut_row"]), 2]
+    for a, b in INTERIORS:
+        Q["%d < nefc < %d" % (a, b)] = [lambda L, a=a, b=b: a < L["nefc"] < b and not (L["cut_con"] or L["cut_row"]), 8]
+    Q["nefc <= 64, > 20 rows with force"] = [lambda L: 0 < L["nefc"] <= 64 and L["nact"] > 20, 6]
+    Q["nefc <= 64, <= 20 rows with force"] = [lambda L: 0 < L["nefc"] <= 64 and L["nact"] <= 20, 6]
+    Q["warm start kept"] = [lambda L: L["warm_nonzero"] and L["warm"] == "kept", 8]
+    Q["warm start discarded"] = [lambda L: L["warm_nonzero"] and L["warm"] == "discarded", 8]
+    Q["PGS leaves early"] = [lambda L: 0 < L["sweeps"] < 50, 8]
+    Q["PGS runs to iterations"] = [lambda L: L["sweeps"] == 50, 8]
+    Q["nlimit > 0"] = [lambda L: L["nlimit"] > 0, 12]
+    for j in range(28):
+        Q["joint %d low" % j] = [lambda L, j=j: j in L["low"], 1]
+        Q["joint %d high" % j] = [lambda L, j=j: j in L["high"], 1]
+    Q["contact-cut"] = [lambda L: L["cut_con"] and L["ncon"] == MAXCON, 6]
+    Q["row-cut"] = [lambda L: L["cut_row"] and MAXROW - 4 < L["nefc"] <= MAXROW, 6]
+    Q["row-cut inside a pyramid"] = [lambda L: L["cut_row"] and L["straddle"] and MAXROW - 4 < L["nefc"] < MAXROW, 3]
+    Q["row-cut between two contacts"] = [lambda L: L["cut_row"] and not L["straddle"] and L["nefc"] == MAXROW, 2]
+    Q["both cuts"] = [lambda L: L["cut_con"] and L["cut_row"], 2]
+    return Q
+
+
+def _lying(model, rng, lo, hi, p_out, zmax):
+    """A humanoid lying face up or face down near the floor, joints anywhere in their ranges; each joint is put 1e-3..0.05 rad
+    beyond one of its bounds with probability p_out."""
+    q = model.qpos0.copy()
+    q[7:] = rng.uniform(lo, hi) * rng.uniform(0.0, 1.0)
+    out = rng.random(28) < p_out
+    side = rng.random(28) < 0.5
+    eps = rng.uniform(1e-3, 0.05, 28)
+    q[7:] = np.where(out, np.where(side, hi + eps, lo - eps), q[7:])
+    pitch = rng.choice([np.pi / 2, -np.pi / 2]) + rng.normal() * 0.2
+    q[3:7] = [np.cos(pitch / 2), 0, np.sin(pitch / 2), 0]
+    q[2] = rng.uniform(0.02, zmax)
+    return q, rng.normal(size=34) * 0.3
+
+
+def _airborne(model, rng, lo, hi, which):
+    """Two metres up, small joint angles, the joints of `which` = [(joint, high side?)] beyond that bound: limit rows alone."""
+    q = model.qpos0.copy()
+    q[2] = 2.0
+    q[7:] = rng.uniform(lo, hi) * 0.1
+    for j, high in which:
+        q[7 + j] = (hi[j] if high else lo[j]) + (1 if high else -1) * rng.uniform(1e-3, 0.05)
+    return q, rng.normal(size=34) * 0.3
+
+
+def humanoid_states(model, seed=20240607, max_draws=40000):
+    """-> dict(qpos [n, 35], qvel [n, 34], warm [n, 34] (all fp32-exact float64), labels [n] of dicts, counts {quota: met},
+    quotas {quota: wanted}, draws).  Deterministic in (model, seed); cached per session."""
+    key = ("humanoid", seed, max_draws)
+    if key in _CACHE:
+        return _CACHE[key]
+    P = _Probe(model)
+    rng = np.random.default_rng(seed)
+    Q = _humanoid_quotas()
+    met = {k: 0 for k in Q}
+    states = []
+
+    def offer(q, v, w, family, only=None):
+        """Label the state; keep it if it fills a quota that is still short.  `only`: the quotas this draw may count for (the
+        warm-started repeats of a pose count for the warm-start quotas alone, so every other quota counts distinct poses)."""
+        q, v, w = _f32(q), _f32(v), _f32(w)
+        lab = P.evaluate(q, v, w)
+        if lab is None:
+            return None
+        names = list(Q) if only is None else only
+        hits = [k for k in names if met[k] < Q[k][1] and Q[k][0](lab)]
+        if not hits:
+            return lab
+        qacc = P.sim.get("qacc").copy()
+        lab["ref"] = P.reference()
+        lab["stable"] = lab["nefc"] > 0 and P.stable_sweeps(q, v, w, lab["sweeps"])
+        lab["family"] = family
+        for k in names:
+            met[k] += bool(Q[k][0](lab))
+        states.append((q, v, w, lab))
+        lab["qacc_oracle"] = qacc
+        return lab
+
+    # limit rows alone, every joint beyond each bound once: groups of 1, 7, 8 and 9 joints walk the (joint, side) list
+    sides = [(j, False) for j in range(28)] + [(j, True) for j in range(28)]
+    cursor = 0
+    for k in (1, 1, 7, 8, 9, 1, 7, 8, 9, 1):
+        which = [sides[(cursor + i) % 56] for i in range(k)]
+        cursor += k
+        q, v = _airborne(model, rng, P.lo, P.hi, which)
+        offer(q, v, np.zeros(34), "airborne, %d joints beyond a bound" % k)
+    for _ in range(4):
+        q, v = _airborne(model, rng, P.lo, P.hi, [])
+        offer(q, v, np.zeros(34), "airborne")
+    draws = 0
+    while draws < max_draws and any(met[k] < Q[k][1] for k in Q):
+        draws += 1
+        kind = draws % 4
+        p_out, zmax = ((0.0, 0.4), (0.05, 0.4), (0.3, 0.1), (0.8, 0.06))[kind]
+        q, v = _lying(model, rng, P.lo, P.hi, p_out, zmax)
+        lab = offer(q, v, np.zeros(34), "lying, p_out %.2f" % p_out)
+        if lab is None or lab["nefc"] == 0 or "qacc_oracle" not in lab and draws % 8:
+            continue
+        # warm starts: the oracle's own acceleration of this state (kept, as a rule) and its negative (discarded, as a rule)
+        if "qacc_oracle" not in lab:
+            P.forward(_f32(q), _f32(v), np.zeros(34))
+            lab["qacc_oracle"] = P.sim.get("qacc").copy()
+        for sg in (1.0, -1.0):
+            offer(q, v, sg * lab["qacc_oracle"], "lying, p_out %.2f, warm start %+d x own qacc" % (p_out, sg),
+                  only=["warm start kept", "warm start discarded"])
+    out = dict(qpos=np.array([s[0] for s in states]), qvel=np.array([s[1] for s in states]),
+               warm=np.array([s[2] for s in states]), labels=[s[3] for s in states],
+               counts=met, quotas={k: v[1] for k, v in Q.items()}, draws=draws)
+    _CACHE[key] = out
+    return out
+
+
+def describe(lab):
+    """One line for a failure message."""
+    return ("%s: nefc %d ncon %d nlimit %d nact %d sweeps %d warm %s%s%s" %
+            (lab["family"], lab["nefc"], lab["ncon"], lab["nlimit"], lab["nact"], lab["sweeps"], lab["warm"],
+             " CONTACT-CUT" if lab["cut_con"] else "", " ROW-CUT" + (" inside a pyramid" if lab["straddle"] else "") if lab["cut_row"] else ""))
+
+
+# ---------------------------------------------------------------------------------------------------------------- Unitree G1
+def g1_mocap(motion="getup_facedown"):
+    from deepmimic_mujoco_amd.config import MotionConfig
+    from deepmimic_mujoco_amd.mocap import MocapDM
+    key = ("g1 clip", motion)
+    if key not in _CACHE:
+        mc = MocapDM(robot="unitree_g1")
+        mc.load_mocap(MotionConfig(motion, robot="unitree_g1").mocap_path)
+        _CACHE[key] = mc
+    return _CACHE[key]
+
+
+def g1_states(seed=7, max_draws=400, row_cut_draws=0):
+    """Frames 0..39 of the face-down getup clip pressed 2..9 cm into the floor, joints +-0.5 rad off the clip, caps 48 / 256.
+    -> dict(qpos [n, 44], qvel [n, 43], labels [n]: dict(kind "cut" | "control" | "row-cut", ncon, nefc), draws, row_cut_draws).
+    With row_cut_draws > 0 a second family (the same frames, every joint beyond a bound with probability 0.9) is searched for
+    states of more than 256 rows."""
+    from oracle import oracle_g1 as og
+    key = ("g1", seed, max_draws, row_cut_draws)
+    if key in _CACHE:
+        return _CACHE[key]
+    g, _ = og.g1_model()
+    mc = g1_mocap()
+    rng = np.random.default_rng(seed)
+    s = og.G1Sim()
+    s.set_caps(G1_MAXCON, G1_MAXROW)
+    lo, hi = np.array(g.jnt_range)[1:, 0], np.array(g.jnt_range)[1:, 1]
+    margin = np.asarray(g.geom_margin)
+    states = {"cut": [], "control": [], "row-cut": []}
+
+    def offer(q, v):
+        q, v = _f32(q), _f32(v)
+        oc, orow = s.geti("overflow_con"), s.geti("overflow_row")
+        s.set("qacc_warmstart", np.zeros(43))
+        if s.set_state(q, v) != 0:
+            return
+        dcon, drow = s.geti("overflow_con") - oc, s.geti("overflow_row") - orow
+        cons = s.contacts()
+        if any(abs(c["dist"] - max(margin[c["geom1"]], margin[c["geom2"]])) < TIE_DIST for c in cons):
+            return
+        if np.any(np.abs(q[7:] - lo) < TIE_LIMIT) or np.any(np.abs(q[7:] - hi) < TIE_LIMIT):
+            return
+        lab = dict(ncon=len(cons), nefc=s.geti("nefc"), cut_con=dcon > 0, cut_row=drow > 0)
+        if drow > 0:
+            kind = "row-cut"
+        elif dcon > 0 and len(cons) == G1_MAXCON:
+            kind = "cut"
+        elif dcon == 0 and 40 <= len(cons) <= G1_MAXCON:
+            kind = "control"
+        else:
+            return
+        if len(states[kind]) < 8:
+            lab["kind"] = kind
+            states[kind].append((q, v, lab))
+
+    def pressed():
+        fr = int(rng.integers(0, 40))
+        q = np.array(mc.data_config[fr], np.float64)
+        q[2] -= rng.uniform(0.02, 0.09)
+        q[7:] += rng.uniform(-0.5, 0.5, 37)
+        return q, rng.normal(size=43) * 0.3
+
+    draws = 0
+    while draws < max_draws and (len(states["cut"]) < 8 or len(states["control"]) < 8):
+        draws += 1
+        offer(*pressed())
+    tried = 0
+    while tried < row_cut_draws and len(states["row-cut"]) < 4:
+        tried += 1
+        q, v = pressed()
+        out, side, eps = rng.random(37) < 0.9, rng.random(37) < 0.5, rng.uniform(1e-3, 0.05, 37)
+        q[7:] = np.where(out, np.where(side, hi + eps, lo - eps), q[7:])
+        offer(q, v)
+    allst = states["cut"] + states["control"] + states["row-cut"]
+    out = dict(qpos=np.array([x[0] for x in allst]), qvel=np.array([x[1] for x in allst]), labels=[x[2] for x in allst],
+               draws=draws, row_cut_draws=tried)
+    _CACHE[key] = out
+    return out

@@ -217,7 +217,8 @@ def test_full_size_batch_properties(model, clips, torch_mod):
 def test_wide_constraint_path_and_caps(model, clips, oracle_clips, torch_mod):
     """Lying poses: ~19 floor contacts x 4 pyramid rows = 76+ rows take the two-rows-per-lane path
     (65..128 rows).  Contact lists, row counts and qacc must match the oracle (caps 32 contacts / 128 rows);
-    a dynamic step from such a pose must agree too."""
+    a dynamic step from such a pose must agree too.  (The poses here stay under both caps; states cut by the 32-contact or the
+    128-row cap, and the boundaries 64 | 65 and 127 | 128, are in tests/test_constraint_paths_gpu.py.)"""
     from oracle.oracle import OracleSim
     torch = torch_mod
     rng = np.random.default_rng(11)
