@@ -29,6 +29,7 @@ EXPORTS = ["dm_default_config", "dm_create", "dm_destroy", "dm_last_error", "dm_
            "dm_rollout_store", "dm_policy_pack", "dm_policy_forward", "dm_policy_packed_floats", "dm_ppo_mlp_grad", "dm_ppo_mlp_workspace_floats", "dm_flat_adam_update", "dm_flat_adam_step_gather", "dm_colsum", "dm_set_seed",
            "dm_linear_tanh", "dm_tanh_linear_wgrad", "dm_tanh_bwd_colsum",
            "dm_ppo_wide_grad", "dm_ppo_wide_packed_elems", "dm_ppo_wide_dp", "dm_ppo_wide_supported",
+           "dm_ppo_wide3_grad", "dm_ppo_wide3_packed_elems", "dm_ppo_wide3_supported",
            "dm_sac_act", "dm_sac_store", "dm_sac_gather", "dm_sac_head_fwd", "dm_sac_critic_loss", "dm_sac_actor_loss",
            "dm_sac_head_bwd", "dm_sac_linear_relu", "dm_sac_relu_bwd_colsum", "dm_sac_polyak",
            "dm_rollout_finish", "dm_rollout_finish_workspace_bytes",
@@ -85,6 +86,10 @@ class DmPpoWideStep(DmPpoStepHead):
                 ("zero_ptr", C.c_void_p), ("zero_floats", C.c_longlong), ("adam_state2", C.c_void_p), ("loss_acc", C.c_void_p)]
 
 
+class DmPpoWide3Step(DmPpoWideStep):
+    """include/deepmimic_hip.h: DmPpoWide3Step — DmPpoWideStep's layout; every bf16 scratch array holds two planes (hi, lo)"""
+
+
 # floats of the state2 buffer of dm_flat_adam_*: {scratch, step count, DM_ADAM_PARTIALS partial sums} (include/deepmimic_hip.h)
 ADAM_STATE_FLOATS = 2 + 1024
 
@@ -135,6 +140,9 @@ def load_library():
     L.dm_ppo_wide_packed_elems.argtypes = [i32, i32, i32]
     L.dm_ppo_wide_dp.argtypes = [i32]
     L.dm_ppo_wide_supported.argtypes = [i32] * 5
+    L.dm_ppo_wide3_grad.argtypes = [C.POINTER(DmPpoWide3Step), vp]
+    L.dm_ppo_wide3_packed_elems.argtypes = [i32, i32, i32]
+    L.dm_ppo_wide3_supported.argtypes = [i32] * 5
     L.dm_policy_pack.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, vp]
     L.dm_policy_forward.argtypes = [vp] + [i32] * 5 + [vp] * 9 + [C.c_uint64, vp, C.c_uint32, i32] + [vp] * 9
     L.dm_policy_forward_bf16.argtypes = L.dm_policy_forward.argtypes
@@ -175,7 +183,7 @@ def load_library():
     L.dm_rollout_finish.argtypes = [i32, i32, vp, vp, i32, vp, vp, C.c_double, C.c_double] + [vp] * 7 + [C.c_longlong, vp]
     for name in EXPORTS:
         if name not in ("dm_default_config", "dm_last_error"):
-            getattr(L, name).restype = C.c_longlong if name in ("dm_policy_packed_floats", "dm_ppo_mlp_workspace_floats", "dm_ppo_wide_packed_elems", "dm_rollout_finish_workspace_bytes") else C.c_int
+            getattr(L, name).restype = C.c_longlong if name in ("dm_policy_packed_floats", "dm_ppo_mlp_workspace_floats", "dm_ppo_wide_packed_elems", "dm_ppo_wide3_packed_elems", "dm_rollout_finish_workspace_bytes") else C.c_int
     _LIB = L
     return L
 

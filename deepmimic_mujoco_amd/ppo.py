@@ -366,6 +366,41 @@ class WideMlpGrad(_FusedGrad):
         return bool(_lib.load_library().dm_ppo_wide_supported(int(B), *net[2:]))
 
 
+class WideMlpGrad3(_FusedGrad):
+    """One minibatch gradient of the WIDE net at fp32 accuracy on the bf16 matrix pipe (`dm_ppo_wide3_grad`, csrc/dm_ppo_wide3.hip;
+    ``PPO(mlp_dtype="bf16x3")``): every operand of a product is carried as two bf16 planes (hi + lo) and a product is three MFMAs.
+    The launches, folds and gradient arena are ``WideMlpGrad``'s; every bf16 scratch array holds two planes."""
+
+    entry = "dm_ppo_wide3_grad"
+
+    def __init__(self, policy, opt, B, loss_acc):
+        st = _lib.DmPpoWide3Step()
+        self._head(st, policy, opt, B)
+        dev, L = self.dev, _lib.load_library()
+        D, H1, H2 = st.D, st.H1, st.H2
+        Dp = int(L.dm_ppo_wide_dp(D))
+        bf = lambda *shape: torch.zeros(*shape, device=dev, dtype=torch.bfloat16)      # leading 2: the planes
+        npk = int(L.dm_ppo_wide3_packed_elems(D, H1, H2))
+        self.buf = dict(wpk=[bf(npk), bf(npk)], xbT=bf(2, (Dp + 31) // 32 * 32, B), h1T=[bf(2, H1, B), bf(2, H1, B)],
+                        dz1T=[bf(2, H1, B), bf(2, H1, B)], h2T=[bf(2, H2, B), bf(2, H2, B)], dz2T=[bf(2, H2, B), bf(2, H2, B)],
+                        dz3T=[bf(2, 32, B), bf(2, 32, B)], part=torch.zeros(2 * (B // 32) * 40, device=dev),
+                        stats8=torch.zeros(8, device=dev), out8=torch.zeros(8, device=dev))
+        self.out8 = self.buf["out8"]
+        for t in range(2):
+            for k in ("wpk", "h1T", "dz1T", "h2T", "dz2T", "dz3T"):
+                getattr(st, k)[t] = self.buf[k][t].data_ptr()
+        st.xbT, st.part, st.stats8, st.out8 = (self.buf[k].data_ptr() for k in ("xbT", "part", "stats8", "out8"))
+        st.zero_ptr, st.zero_floats = opt.flat_g.data_ptr(), opt.n
+        st.adam_state2, st.loss_acc = opt.state2.data_ptr(), loss_acc.data_ptr()
+
+    @staticmethod
+    def supported(policy, B):
+        net = two_hidden_layers(policy)
+        if net is None or policy.log_std.device.type != "cuda":
+            return False
+        return bool(_lib.load_library().dm_ppo_wide3_supported(int(B), *net[2:]))
+
+
 class ExtractedPolicy:
     """The reference's exported walk policy: a = tanh(tanh(o W0 + B0) W2 + B2) WA + BA
     (src/extracted_policy.py:471-478; used with obs[:66] and clip +-0.5, src/play_extracted.py:36-38)."""
@@ -631,8 +666,19 @@ class PPO:
                                               capturable=on_gpu and self.use_hip_graph)
         # mixed-precision learner (library-GEMM path only): bf16 MFMA GEMMs and activations against bf16 shadows of the fp32
         # master weights, fp32 loss / gradients-arena / Adam.  fp32 (the reference's dtype) is the default.
+        # "bf16x3": the reference's precision on the bf16 matrix pipe for nets beyond the fused fp32 [256,128] class (split operands,
+        # three MFMAs per product: WideMlpGrad3); the fused fp32 kernel where it applies, the fp32 library path for anything else
+        if not any(mlp_dtype is v or mlp_dtype == v for v in (torch.float32, torch.bfloat16, "bf16x3")):
+            raise ValueError("mlp_dtype must be torch.float32, torch.bfloat16 or \"bf16x3\", not %r" % (mlp_dtype,))
         self.mlp_dtype = mlp_dtype
         self._wide_ok = False
+        self._wide_cls = WideMlpGrad
+        if mlp_dtype == "bf16x3":
+            if not self.flat_adam:
+                raise ValueError("mlp_dtype=bf16x3 needs the flat Adam path (GPU)")
+            self._wide_cls = WideMlpGrad3
+            self._wide_ok = (bool(fused_wide) and self.fused_loss and WideMlpGrad3.supported(self.policy, self.batch_size)
+                             and not (self.fused_mlp and FusedMlpGrad.supported(self.policy, self.batch_size)))
         if mlp_dtype == torch.bfloat16:
             if not self.flat_adam:
                 raise ValueError("mlp_dtype=bfloat16 needs the flat Adam path (GPU)")
@@ -688,6 +734,26 @@ class PPO:
         step, driver = route(self) if self._collector is None else (self._collector.step_kind, self._collector.driver)
         return step if step == "policy_forward" or driver != "captured" else "graph"
 
+    def _grad_route(self, B, on_gpu=True):
+        """Which code forms the gradient of a minibatch of B rows on the flat-Adam paths: "fused" (dm_ppo_mlp_grad), "wide"
+        (dm_ppo_wide_grad / dm_ppo_wide3_grad) or "library" (library GEMMs).  The one predicate ``_minibatch_grad``, ``train`` and
+        ``learner_path`` route by."""
+        if self.fused_mlp and self.fused_loss and on_gpu and FusedMlpGrad.supported(self.policy, B):
+            return "fused"
+        if self._wide_ok and on_gpu and B == self.batch_size:
+            return "wide"
+        return "library"
+
+    def learner_path(self):
+        """Name of the minibatch-gradient path a full minibatch takes, for run records: "fused_fp32" (dm_ppo_mlp_grad), "wide_bf16"
+        (dm_ppo_wide_grad), "wide_bf16x3" (dm_ppo_wide3_grad), "library_bf16" or "library_fp32" (library GEMMs)."""
+        route = self._grad_route(self.batch_size, self.device.type == "cuda") if self.flat_adam else "library"
+        if route == "fused":
+            return "fused_fp32"
+        if route == "wide":
+            return "wide_bf16x3" if self._wide_cls is WideMlpGrad3 else "wide_bf16"
+        return "library_bf16" if self.mlp_dtype == torch.bfloat16 else "library_fp32"
+
     def collect_rollouts(self):
         return self.collector().collect()
 
@@ -699,7 +765,7 @@ class PPO:
         loss_sum = torch.zeros((), device=self.device)
         nsteps = 0
         on_dev = (self.flat_adam and self.fused_loss and self.device.type == "cuda" and n % self.batch_size == 0
-                  and ((self.fused_mlp and FusedMlpGrad.supported(self.policy, self.batch_size)) or self._wide_ok))
+                  and self._grad_route(self.batch_size) != "library")
         self._on_dev = on_dev
         if on_dev:
             self._loss_acc.zero_()
@@ -795,7 +861,8 @@ class PPO:
         """Gradient half of an optimizer step on the flat-Adam paths: leaves the minibatch gradient in ``optimizer.flat_g``
         (the operand of the ONE collective of the data-parallel learner).  Returns (loss, begin): begin is False when Adam's
         begin launch was folded into the gradient launches (dm_ppo_mlp_grad)."""
-        if (self.fused_mlp and self.fused_loss and obs.is_cuda and FusedMlpGrad.supported(self.policy, obs.shape[0])):
+        route = self._grad_route(obs.shape[0], obs.is_cuda)
+        if route == "fused":
             # the whole minibatch gradient in three launches, written into the flat arena
             # (that launch sequence also clears the arena, performs Adam's begin and adds the loss to a device-side sum)
             mg = self._mlp_grads.get(obs.shape[0])
@@ -804,11 +871,11 @@ class PPO:
             loss = mg(obs.contiguous(), act.contiguous(), adv.contiguous(), ret.contiguous(), old_logp.contiguous(), self.clip_range,
                       self.vf_coef, self.ent_coef, self.normalize_advantage and obs.shape[0] > 1)
             return loss, False
-        if self._wide_ok and obs.is_cuda and obs.shape[0] == self.batch_size:
-            # wide nets with bf16 matrix-pipe products: the fused chain of dm_ppo_wide_grad + six library weight-gradient GEMMs
+        if route == "wide":
+            # wide nets with matrix-pipe products (bf16: WideMlpGrad, split bf16: WideMlpGrad3): pack, fused chain, weight gradients
             wg = self._mlp_grads.get(("wide", obs.shape[0]))
             if wg is None:
-                wg = self._mlp_grads[("wide", obs.shape[0])] = WideMlpGrad(self.policy, self.optimizer, obs.shape[0], self._loss_acc)
+                wg = self._mlp_grads[("wide", obs.shape[0])] = self._wide_cls(self.policy, self.optimizer, obs.shape[0], self._loss_acc)
             loss = wg(obs.contiguous(), act.contiguous(), adv.contiguous(), ret.contiguous(), old_logp.contiguous(), self.clip_range,
                       self.vf_coef, self.ent_coef, self.normalize_advantage and obs.shape[0] > 1)
             return loss, False

@@ -39,6 +39,9 @@ def main(argv=None):
     ap.add_argument("--bf16-learner", action="store_true",
                     help="PPO(mlp_dtype=bfloat16): bf16 matrix-pipe products in the learner (dm_ppo_wide_grad for [256,128] .. [1024,512]-class "
                          "nets; fp32 master weights, loss, gradients and Adam) — 106 us instead of 378 us per optimizer step on MLP(1024,512)")
+    ap.add_argument("--bf16x3-learner", action="store_true",
+                    help="PPO(mlp_dtype=\"bf16x3\"): the reference's fp32 accuracy on the bf16 matrix pipe for nets beyond the fused fp32 "
+                         "[256,128] class (dm_ppo_wide3_grad: split operands, three MFMAs per product); not with --bf16-learner")
     ap.add_argument("--save", default="")
     ap.add_argument("--sub-batches", type=int, default=1,
                     help="> 1: the env batch as that many engines, each on its own probed concurrent HIP stream (double-buffered rollout: "
@@ -51,6 +54,8 @@ def main(argv=None):
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="gloo + several ranks on one GPU only rehearses the multi-rank path")
     args = ap.parse_args(argv)
+    if args.bf16_learner and args.bf16x3_learner:
+        ap.error("--bf16-learner and --bf16x3-learner are mutually exclusive")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if args.algo == "sac" and world > 1:
@@ -85,7 +90,7 @@ def main(argv=None):
     ppo = PPO(env, net_arch=tuple(int(x) for x in args.arch.split(",")), n_steps=args.horizon,
               batch_size=args.minibatch, n_epochs=args.epochs, learning_rate=args.lr, seed=args.seed,
               buffer_dtype=torch.bfloat16 if args.bf16_buffer else torch.float32, rollout_graph=args.rollout_graph,
-              mlp_dtype=torch.bfloat16 if args.bf16_learner else torch.float32)
+              mlp_dtype=torch.bfloat16 if args.bf16_learner else "bf16x3" if args.bf16x3_learner else torch.float32)
     hist = []
     dash = None
     if args.eval_every > 0 and rank == 0:                               # src/sb3_ppo.py:273-313: one eval env next to the batch
@@ -118,6 +123,7 @@ def main(argv=None):
             print(json.dumps({"workload": "ppo", "n_gpus": world, "envs_per_gpu": args.envs, "horizon": args.horizon,
                               "arch": args.arch, "epochs": args.epochs, "minibatch": args.minibatch,
                               "buffer_dtype": str(ppo.buffer_dtype).replace("torch.", ""), "rollout_path": ppo.rollout_path(),
+                              "learner": ppo.learner_path(),
                               "iterations": len(hist), "rollout_env_steps_per_s": per_it / roll,
                               "train_s_per_iter": trn, "overall_env_steps_per_s": per_it / (roll + trn),
                               "mean_reward_last": hist[-1]["mean_reward"], "wall_s": dt,
