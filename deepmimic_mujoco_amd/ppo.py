@@ -335,21 +335,23 @@ class WideMlpGrad(_FusedGrad):
     """One minibatch gradient of the WIDE net ([1024,512]-class, the net BASELINE configs 3-5 name) with bf16 matrix-pipe products
     (`dm_ppo_wide_grad`, csrc/dm_ppo_wide.hip): weights -> bf16, the fused forward / loss / input-gradient chain of both trunks, the
     six weight gradients — three launches.  fp32 master weights, fp32 loss, gradients and Adam.  Leaves every gradient in
-    ``opt.flat_g`` (cleared by the first launch, which also performs Adam's begin) and adds the loss to ``loss_acc``."""
+    ``opt.flat_g`` (cleared by the first launch, which also performs Adam's begin) and adds the loss to ``loss_acc``.  The class
+    attributes name the entry point, its step struct and size / support calls, and the bf16 planes per scratch array."""
 
-    entry = "dm_ppo_wide_grad"
+    entry, step_cls, planes = "dm_ppo_wide_grad", "DmPpoWideStep", 1
+    packed_elems, supported_fn = "dm_ppo_wide_packed_elems", "dm_ppo_wide_supported"
 
     def __init__(self, policy, opt, B, loss_acc):
-        st = _lib.DmPpoWideStep()
+        st = getattr(_lib, self.step_cls)()
         self._head(st, policy, opt, B)
         dev, L = self.dev, _lib.load_library()
         D, H1, H2 = st.D, st.H1, st.H2
         Dp = int(L.dm_ppo_wide_dp(D))
-        bf = lambda *shape: torch.zeros(*shape, device=dev, dtype=torch.bfloat16)
-        npk = int(L.dm_ppo_wide_packed_elems(D, H1, H2))
-        self.buf = dict(wpk=[bf(npk), bf(npk)], xbT=bf((Dp + 31) // 32 * 32, B), h1T=[bf(H1, B), bf(H1, B)], dz1T=[bf(H1, B), bf(H1, B)], h2T=[bf(H2, B), bf(H2, B)],
-                        dz2T=[bf(H2, B), bf(H2, B)], dz3T=[bf(32, B), bf(32, B)], part=torch.zeros(2 * (B // 32) * 40, device=dev),
-                        stats8=torch.zeros(8, device=dev), out8=torch.zeros(8, device=dev))
+        bf = lambda n: torch.zeros(self.planes * n, device=dev, dtype=torch.bfloat16)      # every bf16 array: `planes` planes of n elements
+        npk = int(getattr(L, self.packed_elems)(D, H1, H2)) // self.planes
+        self.buf = dict(wpk=[bf(npk), bf(npk)], xbT=bf((Dp + 31) // 32 * 32 * B), h1T=[bf(H1 * B), bf(H1 * B)], dz1T=[bf(H1 * B), bf(H1 * B)],
+                        h2T=[bf(H2 * B), bf(H2 * B)], dz2T=[bf(H2 * B), bf(H2 * B)], dz3T=[bf(32 * B), bf(32 * B)],
+                        part=torch.zeros(2 * (B // 32) * 40, device=dev), stats8=torch.zeros(8, device=dev), out8=torch.zeros(8, device=dev))
         self.out8 = self.buf["out8"]
         for t in range(2):
             for k in ("wpk", "h1T", "dz1T", "h2T", "dz2T", "dz3T"):
@@ -358,47 +360,21 @@ class WideMlpGrad(_FusedGrad):
         st.zero_ptr, st.zero_floats = opt.flat_g.data_ptr(), opt.n
         st.adam_state2, st.loss_acc = opt.state2.data_ptr(), loss_acc.data_ptr()
 
-    @staticmethod
-    def supported(policy, B):
+    @classmethod
+    def supported(cls, policy, B):
         net = two_hidden_layers(policy)
         if net is None or policy.log_std.device.type != "cuda":
             return False
-        return bool(_lib.load_library().dm_ppo_wide_supported(int(B), *net[2:]))
+        return bool(getattr(_lib.load_library(), cls.supported_fn)(int(B), *net[2:]))
 
 
-class WideMlpGrad3(_FusedGrad):
+class WideMlpGrad3(WideMlpGrad):
     """One minibatch gradient of the WIDE net at fp32 accuracy on the bf16 matrix pipe (`dm_ppo_wide3_grad`, csrc/dm_ppo_wide3.hip;
     ``PPO(mlp_dtype="bf16x3")``): every operand of a product is carried as two bf16 planes (hi + lo) and a product is three MFMAs.
     The launches, folds and gradient arena are ``WideMlpGrad``'s; every bf16 scratch array holds two planes."""
 
-    entry = "dm_ppo_wide3_grad"
-
-    def __init__(self, policy, opt, B, loss_acc):
-        st = _lib.DmPpoWide3Step()
-        self._head(st, policy, opt, B)
-        dev, L = self.dev, _lib.load_library()
-        D, H1, H2 = st.D, st.H1, st.H2
-        Dp = int(L.dm_ppo_wide_dp(D))
-        bf = lambda *shape: torch.zeros(*shape, device=dev, dtype=torch.bfloat16)      # leading 2: the planes
-        npk = int(L.dm_ppo_wide3_packed_elems(D, H1, H2))
-        self.buf = dict(wpk=[bf(npk), bf(npk)], xbT=bf(2, (Dp + 31) // 32 * 32, B), h1T=[bf(2, H1, B), bf(2, H1, B)],
-                        dz1T=[bf(2, H1, B), bf(2, H1, B)], h2T=[bf(2, H2, B), bf(2, H2, B)], dz2T=[bf(2, H2, B), bf(2, H2, B)],
-                        dz3T=[bf(2, 32, B), bf(2, 32, B)], part=torch.zeros(2 * (B // 32) * 40, device=dev),
-                        stats8=torch.zeros(8, device=dev), out8=torch.zeros(8, device=dev))
-        self.out8 = self.buf["out8"]
-        for t in range(2):
-            for k in ("wpk", "h1T", "dz1T", "h2T", "dz2T", "dz3T"):
-                getattr(st, k)[t] = self.buf[k][t].data_ptr()
-        st.xbT, st.part, st.stats8, st.out8 = (self.buf[k].data_ptr() for k in ("xbT", "part", "stats8", "out8"))
-        st.zero_ptr, st.zero_floats = opt.flat_g.data_ptr(), opt.n
-        st.adam_state2, st.loss_acc = opt.state2.data_ptr(), loss_acc.data_ptr()
-
-    @staticmethod
-    def supported(policy, B):
-        net = two_hidden_layers(policy)
-        if net is None or policy.log_std.device.type != "cuda":
-            return False
-        return bool(_lib.load_library().dm_ppo_wide3_supported(int(B), *net[2:]))
+    entry, step_cls, planes = "dm_ppo_wide3_grad", "DmPpoWide3Step", 2
+    packed_elems, supported_fn = "dm_ppo_wide3_packed_elems", "dm_ppo_wide3_supported"
 
 
 class ExtractedPolicy:

@@ -401,28 +401,12 @@ int dm_ppo_wide_grad(const DmPpoWideStep *step, void *stream);
  * fp32.  Three plain launches, capturable.  The head of the struct (B .. g_log_std), the folds (zero_ptr, adam_state2, loss_acc), the
  * ACCUMULATE semantics of the gradients, out8 and the refusals (DM_EINVAL before any launch for an unsupported shape or a NULL required
  * pointer) are DmPpoWideStep's.  Every bf16 scratch array is TWO planes in the same fragment order: plane 0 = hi, plane 1 = lo,
- * starting at the one-plane element count (the size dm_ppo_wide_grad asks for); so each array has twice DmPpoWideStep's size.
+ * starting at the one-plane element count (the size dm_ppo_wide_grad asks for); so each array has twice DmPpoWideStep's size:
+ * wpk dm_ppo_wide3_packed_elems(D, H1, H2) elements per trunk, xbT 2 * (dm_ppo_wide_dp(D) rounded up to 32) * B, h1T / dz1T 2 * H1 * B,
+ * h2T / dz2T 2 * H2 * B, dz3T 2 * 32 * B; part, stats8 and out8 are fp32 and keep their sizes.
  * Supported: exactly the shapes of dm_ppo_wide_supported (the chain holds layer 1 in 256-column chunks: H1 does not enter its LDS
  * need).  With split-K 1 (see dm_ppo_wide_grad) the weight gradients are bit-reproducible. */
-typedef struct DmPpoWide3Step {
-  int32_t B, D, H1, H2, A, normalize_advantage;
-  float clip_range, vf_coef, ent_coef;
-  int32_t reserved;
-  const float *obs, *act, *adv, *ret, *old_logp, *log_std;
-  const float *W[2][3], *b[2][3];
-  float *gW[2][3], *gb[2][3];
-  float *g_log_std;
-  void *wpk[2];                 /* bf16 scratch, dm_ppo_wide3_packed_elems(D, H1, H2) elements per trunk (both planes) */
-  void *xbT;                    /* bf16 scratch, 2 * (dm_ppo_wide_dp(D) rounded up to 32) * B elements */
-  void *h1T[2], *dz1T[2];       /* bf16 scratch, 2 * H1 * B elements each */
-  void *h2T[2], *dz2T[2];       /* bf16 scratch, 2 * H2 * B elements each */
-  void *dz3T[2];                /* bf16 scratch, 2 * 32 * B elements each */
-  float *part;                  /* scratch, 2 * (B / 32) * 40 floats */
-  float *stats8, *out8;         /* 8 floats each */
-  float *zero_ptr;              /* optional folds, as DmPpoMlpStep */
-  long long zero_floats;
-  float *adam_state2, *loss_acc;
-} DmPpoWide3Step;
+typedef DmPpoWideStep DmPpoWide3Step;
 long long dm_ppo_wide3_packed_elems(int D, int H1, int H2);      /* both planes: 2 * dm_ppo_wide_packed_elems(D, H1, H2) */
 int dm_ppo_wide3_supported(int B, int D, int H1, int H2, int A);
 int dm_ppo_wide3_grad(const DmPpoWide3Step *step, void *stream);

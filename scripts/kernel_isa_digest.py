@@ -7,7 +7,7 @@
 
 Each unit is compiled with the Makefile's FLAGS plus `--cuda-device-only -S`; the assembly is cut at the function labels,
 comments are dropped and the function index in local labels (.LBB<n>_) is normalised, so a kernel that merely moved to
-another file or position hashes the same.  Next to it go the digest of the sorted mnemonics (equal = the same instructions in
+another file or position hashes the same; --compare matches kernels by their name up to the parameter list.  Next to it go the digest of the sorted mnemonics (equal = the same instructions in
 another order) and the kernel's register counts and segment sizes from the metadata.  Text is hashed and compared, nothing else.
 """
 import argparse, hashlib, json, os, re, subprocess, sys, tempfile
@@ -50,6 +50,24 @@ def digest_unit(csrc, unit, hipcc, flags):
     return out
 
 
+def by_name(D):
+    """Keys cut before the parameter list (_ZN <length><identifier>.. E <parameters>), where that stays unique: a kernel whose
+    argument struct was renamed keeps its entry."""
+    def cut(k):
+        name, at, unit = k.partition("@")
+        i = 3 if name.startswith("_ZN") else len(name)
+        while i < len(name) and name[i].isdigit():
+            j = i
+            while name[j].isdigit():
+                j += 1
+            i = j + int(name[i:j])
+        return name[:i] + at + unit
+    short = {}
+    for k in D:
+        short.setdefault(cut(k), []).append(k)
+    return {(c if len(ks) == 1 else k): D[k] for c, ks in short.items() for k in ks}
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--csrc", default=CSRC)
@@ -58,7 +76,7 @@ def main():
     ap.add_argument("--compare", nargs=2, metavar=("A.json", "B.json"))
     a = ap.parse_args()
     if a.compare:
-        A, B = (json.load(open(p)) for p in a.compare)
+        A, B = (by_name(json.load(open(p))) for p in a.compare)
         diff = sorted(k for k in set(A) | set(B) if A.get(k, {}).get("sha256") != B.get(k, {}).get("sha256"))
         same_ops = {k: k in A and k in B and all(A[k][f] == B[k][f] for f in ("opcodes_sha256", "meta")) for k in diff}
         print(json.dumps({"entries": [len(A), len(B)], "differ": diff, "same_opcodes_and_metadata": same_ops}, indent=1))
