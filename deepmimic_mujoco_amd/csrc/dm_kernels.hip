@@ -51,6 +51,8 @@
 #define PROF(i) do {} while (0)
 #endif
 typedef __attribute__((address_space(3))) const float *lds_cfloat_p;
+typedef float lds_f2v __attribute__((ext_vector_type(2)));
+typedef float lds_f4v __attribute__((ext_vector_type(4)));
 typedef float mfma_f16v __attribute__((ext_vector_type(16)));
 #ifndef DMK_MFMA_MIN_ROWS
 #define DMK_MFMA_MIN_ROWS 8   // below this the 17-MFMA product (1088 cycles) loses to nefc x (34 v_readlane + 34 FMA)
@@ -125,6 +127,28 @@ __device__ __forceinline__ float solve_L(float x, const float dv, const int mrow
     return true;
   });
   return x;
+}
+// Row I of the factor without its diagonal (the NANC[I] ancestor entries, nearest ancestor first) and dinv[I], read
+// through a pointer to the 16-byte aligned EnvLds with the widest loads the entries' alignment allows.
+template <int I, int K = 0>
+__device__ __forceinline__ void load_factor_row(lds_cfloat_p Sp, float (&W)[DMK_MAXANC], float &dinv) {
+  static_assert(alignof(EnvLds) >= 16 && offsetof(EnvLds, M) % 4 == 0 && offsetof(EnvLds, dinv) % 4 == 0, "EnvLds layout");
+  constexpr int n = topo::NANC[I];
+  constexpr int a = (int)(offsetof(EnvLds, M) / 4) + topo::MADR[I] + 1 + K;   // float index from the start of EnvLds
+  if constexpr (K >= n) {
+    dinv = Sp[offsetof(EnvLds, dinv) / 4 + I];
+  } else if constexpr (a % 4 == 0 && n - K >= 4) {
+    const lds_f4v v = *reinterpret_cast<__attribute__((address_space(3))) const lds_f4v *>(Sp + a);
+    W[K] = v.x; W[K + 1] = v.y; W[K + 2] = v.z; W[K + 3] = v.w;
+    load_factor_row<I, K + 4>(Sp, W, dinv);
+  } else if constexpr (a % 2 == 0 && n - K >= 2) {
+    const lds_f2v v = *reinterpret_cast<__attribute__((address_space(3))) const lds_f2v *>(Sp + a);
+    W[K] = v.x; W[K + 1] = v.y;
+    load_factor_row<I, K + 2>(Sp, W, dinv);
+  } else {
+    W[K] = Sp[a];
+    load_factor_row<I, K + 1>(Sp, W, dinv);
+  }
 }
 template <int CTRL>
 __device__ __forceinline__ float dpp_mov(float v) {
@@ -1135,7 +1159,9 @@ __device__ __forceinline__ int fwd_collide(GDev &T, const int lane) {
 
 // ---- one constraint row (limit or pyramid edge / frictionless contact) for the calling lane:
 // Jacobian row -> reference acceleration, regulariser -> B row = D^-1/2 L^-T J^T (returned in J)
-template <bool MF>   // MF: all rows live in lanes 0..31 (nefc <= 32): the dof-by-row products run on the matrix pipe
+// MF: all rows live in lanes 0..31 (nefc <= 32): the dof-by-row products run on the matrix pipe.  PF: the back-substitution
+// prefetches the factor two rows ahead; off on the wide path, whose two rows per lane leave no registers for the windows.
+template <bool MF, bool PF = true>
 __device__ __forceinline__ void build_row(GDev &T, EnvLds &S, const int r, const int nefc, const float (&com)[3],
                                           float (&J)[DMK_NV], float &R, float &Dd, float &aref, float &bb, float &jw) {
       float rpos = 0, rmargin = 0, rdiag = 1, mu = 0;
@@ -1240,15 +1266,51 @@ __device__ __forceinline__ void build_row(GDev &T, EnvLds &S, const int r, const
       {
         // x <- L^-T x on the row held by this lane: only the 276 ancestor pairs of the dof tree, all
         // register and LDS indices static (dm_topology.h); factor entries are wave-uniform broadcasts.
-        // Step i's loads are tied to step i+1's result so they are not all hoisted ahead of the FMAs.
-        lds_cfloat_p Mp = (lds_cfloat_p)S.M;
+        // The factor does not depend on J, so it is prefetched: W / dn hold row i and dinv[i], W1 / dn1 row i-1, and row i-2
+        // is requested before step i's FMAs and waited for once, two steps later (one step ahead still left 43 k of the
+        // parent's 50 k cycles in this phase, two leave 41 k: DESIGN §3).  The request is tied to J[i], final when step i
+        // starts, so that the 276 loads are not all hoisted ahead of the FMAs.
+        if constexpr (PF) {
+          lds_cfloat_p Sp = (lds_cfloat_p)&S;
+          float W[DMK_MAXANC], dn, W1[DMK_MAXANC], dn1;
+          load_factor_row<DMK_NV - 1>(Sp, W, dn);
+          load_factor_row<DMK_NV - 2>(Sp, W1, dn1);
+          StaticFor<0, DMK_NV - 1>::run([&](auto ic) {
+            constexpr int i = DMK_NV - 1 - decltype(ic)::value;   // 33 .. 1
+            const float xi = J[i] * dn;
+            float Wn[DMK_MAXANC], dnn = 0.f;
+            if constexpr (i > 2) {
+              asm volatile("" : "+v"(Sp), "+v"(J[i]));
+              load_factor_row<i - 2>(Sp, Wn, dnn);
+            }
+            StaticFor<0, i>::run([&](auto jc) {
+              constexpr int j = decltype(jc)::value;
+              if constexpr (topo::is_anc(j, i)) J[j] -= W[topo::NANC[i] - topo::NANC[j] - 1] * xi;
+              return true;
+            });
+            if constexpr (i > 1) {
 #pragma unroll
-        for (int i = DMK_NV - 1; i >= 1; i--) {
-          const float xi = J[i] * S.dinv[i];
-          asm volatile("" : "+v"(Mp), "+v"(J[0]));
+              for (int k = 0; k < topo::NANC[i - 1]; k++) W[k] = W1[k];
+              dn = dn1;
+            }
+            if constexpr (i > 2) {
 #pragma unroll
-          for (int j = 0; j < i; j++)
-            if (topo::is_anc(j, i)) J[j] -= Mp[topo::midx(i, j)] * xi;
+              for (int k = 0; k < topo::NANC[i - 2]; k++) W1[k] = Wn[k];
+              dn1 = dnn;
+            }
+            return true;
+          });
+        } else {
+          // Step i's loads are tied to step i+1's result so they are not all hoisted ahead of the FMAs.
+          lds_cfloat_p Mp = (lds_cfloat_p)S.M;
+#pragma unroll
+          for (int i = DMK_NV - 1; i >= 1; i--) {
+            const float xi = J[i] * S.dinv[i];
+            asm volatile("" : "+v"(Mp), "+v"(J[0]));
+#pragma unroll
+            for (int j = 0; j < i; j++)
+              if (topo::is_anc(j, i)) J[j] -= Mp[topo::midx(i, j)] * xi;
+          }
         }
       }
 #pragma unroll
@@ -1266,8 +1328,8 @@ __device__ __noinline__ float fwd_constraint_wide(GDev &T, const int lane, const
   const float com[3] = {S.com[0], S.com[1], S.com[2]};
   float Ja[DMK_NV], Jb[DMK_NV];
   float Ra, Da, arefa, bba, jwa, Rb, Db, arefb, bbb, jwb;
-  build_row<false>(T, S, lane, nefc, com, Ja, Ra, Da, arefa, bba, jwa);
-  build_row<false>(T, S, lane + 64, nefc, com, Jb, Rb, Db, arefb, bbb, jwb);
+  build_row<false, false>(T, S, lane, nefc, com, Ja, Ra, Da, arefa, bba, jwa);
+  build_row<false, false>(T, S, lane + 64, nefc, com, Jb, Rb, Db, arefb, bbb, jwb);
   float ARda = Ra, ARdb = Rb;
 #pragma unroll
   for (int k = 0; k < DMK_NV; k++) { ARda += Ja[k] * Ja[k]; ARdb += Jb[k] * Jb[k]; }
