@@ -33,7 +33,8 @@ EXPORTS = ["dm_default_config", "dm_create", "dm_destroy", "dm_last_error", "dm_
            "dm_sac_act", "dm_sac_store", "dm_sac_gather", "dm_sac_head_fwd", "dm_sac_critic_loss", "dm_sac_actor_loss",
            "dm_sac_head_bwd", "dm_sac_linear_relu", "dm_sac_relu_bwd_colsum", "dm_sac_polyak",
            "dm_rollout_finish", "dm_rollout_finish_workspace_bytes",
-           "dm_policy_forward_bf16", "dm_rollout_store_bf16", "dm_ppo_gather_bf16", "dm_flat_adam_step_gather_bf16"]
+           "dm_policy_forward_bf16", "dm_rollout_store_bf16", "dm_ppo_gather_bf16", "dm_flat_adam_step_gather_bf16",
+           "dm_step_active", "dm_eval_advance"]
 
 
 class DmConfig(C.Structure):
@@ -125,6 +126,8 @@ def load_library():
     L.dm_reset.argtypes = [vp, vp, vp, vp, vp]
     L.dm_step.argtypes = [vp] * 9
     L.dm_step_forced.argtypes = [vp] * 9
+    L.dm_step_active.argtypes = [vp, vp, vp, i32] + [vp] * 6
+    L.dm_eval_advance.argtypes = [i32, i32, i32, vp, vp, vp, vp, vp, i32] + [vp] * 8 + [i32, vp]
     L.dm_physics_step.argtypes = [vp] * 3
     L.dm_set_state.argtypes = [vp, vp, i32, vp, vp, vp, vp, i32, vp]
     L.dm_get_state.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp]
@@ -308,6 +311,7 @@ class HipEngine(EngineBase):
         self.model = model
         self.N = int(num_envs)
         self.device = torch.device("cuda", device)
+        self.auto_reset = bool(auto_reset)
         self.cfg = default_config(num_envs=self.N, device=device, seed=seed,
                                   auto_reset=1 if auto_reset else 0, **cfg_kw)
         h = C.c_void_p()
@@ -331,6 +335,11 @@ class HipEngine(EngineBase):
         t = None if clip_ids is None else clip_ids.to(self.device, self.torch.int32).contiguous()
         self._call("set_env_clips", t)
         self._keep = t
+
+    def step_active(self, actions, env_ids, nslots, out):
+        """``dm_step_active``: the envs listed in ``env_ids[:nslots]`` (int32 device tensor, entries < 0 skipped) take one step without
+        auto-reset; ``actions`` and the rows of ``out`` stay indexed by env."""
+        self._call("step_active", actions, env_ids, int(nslots), out["obs"], out["rew"], out["done"], out.get("terms"), out.get("reason"))
 
     # ---- state
     def physics_step(self, actions):

@@ -355,7 +355,8 @@ static void fill_launch(DmEngine *e, DmLaunch &P, int mode) {
   P.debug = e->debug;
 }
 
-static int launch(DmEngine *e, DmLaunch &P, int nslots, void *stream) {
+// variant_n: the batch size the two- / three-wave choice is made for (0: nslots)
+static int launch(DmEngine *e, DmLaunch &P, int nslots, void *stream, int variant_n = 0) {
   P.nslots = nslots;
   if (e->clipL[0] < 1) return fail(e, DM_EINVAL, "no clip loaded (dm_load_clip clip 0 first)");
   if (e->cfg.task == DM_TASK_COMBINED && (e->clipL[1] < 1 || e->clipL[2] < 2))
@@ -366,7 +367,7 @@ static int launch(DmEngine *e, DmLaunch &P, int nslots, void *stream) {
   const bool rec = e->timing && (e->nlaunch++ % e->stride) == 0;
   if (rec) hipEventRecord(e->ev0[evi], s);
   const dim3 grid((P.nslots + DMK_ENVS_PER_BLOCK - 1) / DMK_ENVS_PER_BLOCK), block(64 * DMK_ENVS_PER_BLOCK);
-  const bool three_waves = e->waves == 3 || (e->waves == 0 && P.nslots >= 3072);
+  const bool three_waves = e->waves == 3 || (e->waves == 0 && (variant_n > 0 ? variant_n : P.nslots) >= 3072);
   if (e->cfg.task == DM_TASK_COMBINED) {
     if (three_waves) hipLaunchKernelGGL(dm_step_combined_kernel_w3, grid, block, 0, s, P);
     else hipLaunchKernelGGL(dm_step_combined_kernel, grid, block, 0, s, P);
@@ -408,6 +409,18 @@ extern "C" int dm_step(DmHandle e, const float *actions, float *obs, float *rew,
     P.env_ids = e->dOrder;
   }
   return launch(e, P, e->N, stream);
+}
+
+extern "C" int dm_step_active(DmHandle e, const float *actions, const int32_t *env_ids, int nslots, float *obs, float *rew,
+                              uint8_t *done, float *terms, int32_t *reason, void *stream) {
+  if (!e || !actions || !env_ids || !obs || !rew || !done || nslots < 1 || nslots > e->N) return fail(e, DM_EINVAL, "dm_step_active: bad argument");
+  DmLaunch P;
+  fill_launch(e, P, DMK_MODE_STEP);
+  P.actions = actions; P.obs = obs; P.rew = rew; P.done = done; P.terms = terms; P.reason = reason;
+  P.cost = e->dCost;
+  P.auto_reset = 0;                      // a finished env keeps its terminal state
+  P.env_ids = env_ids;                   // the caller's order: no longest-first schedule
+  return launch(e, P, nslots, stream, e->N);   // the kernel variant of the whole batch, however few envs are left
 }
 
 extern "C" int dm_physics_step(DmHandle e, const float *actions, void *stream) {

@@ -115,13 +115,35 @@ def _plot_log(log, video_dir):
 
 
 class EvalDashboardCallback:
-    """`callback=` of `PPO.learn`: evaluate every `every_n_global_steps` (src/sb3_ppo.py:143-190; called once per PPO iteration)."""
+    """`callback=` of `PPO.learn`: evaluate every `every_n_global_steps` (src/sb3_ppo.py:143-190; called once per PPO iteration).
 
-    def __init__(self, eval_env, run_name, log_wandb=False, every_n_global_steps=1_000_000, out_root=None, figures=True, max_steps=None):
+    ``batch_env`` (an ``auto_reset=False`` batch env, default None = off): every evaluation point also runs the batched evaluation
+    (evaluation.evaluation_record: one deterministic episode per start frame of ``batch_start_frames``) and appends
+    ``global_step,episodes,ep_rew_mean,ep_rew_std,ep_len_mean,frac_reached_cap`` to ``eval_batch.csv`` next to ``log.csv``."""
+
+    def __init__(self, eval_env, run_name, log_wandb=False, every_n_global_steps=1_000_000, out_root=None, figures=True, max_steps=None,
+                 batch_env=None, batch_start_frames="all"):
         self.eval_env, self.run_name, self.log_wandb = eval_env, run_name, log_wandb
         self.every, self.out_root, self.figures, self.max_steps = every_n_global_steps, out_root, figures, max_steps
+        self.batch_env, self.batch_start_frames = batch_env, batch_start_frames
         self.last_eval = None
         self.history = []
+        self.batch_history = []
+
+    def batch_evaluation(self, model, n):
+        """One batched evaluation point -> its record (also appended to ``eval_batch.csv`` and ``batch_history``)."""
+        from .evaluation import RECORD_FIELDS, evaluation_record
+        rec = evaluation_record(model, self.batch_env, n, start_frames=self.batch_start_frames, max_steps=self.max_steps)
+        video_dir = os.path.join(os.path.expanduser(self.out_root or "~/deep_mimic"), self.run_name + "_videos")
+        os.makedirs(video_dir, exist_ok=True)
+        path = os.path.join(video_dir, "eval_batch.csv")
+        if not os.path.exists(path):
+            with open(path, "w") as f:
+                f.write(",".join(RECORD_FIELDS) + "\n")
+        with open(path, "a") as f:
+            f.write(",".join(repr(rec[k]) for k in RECORD_FIELDS) + "\n")
+        self.batch_history.append(rec)
+        return rec
 
     def __call__(self, model):
         n = int(model.num_timesteps)
@@ -129,4 +151,6 @@ class EvalDashboardCallback:
             self.last_eval = n
             self.history.append((n,) + eval_dashboard_rollout(model, self.eval_env, n, self.run_name, log_wandb=self.log_wandb,
                                                               out_root=self.out_root, max_steps=self.max_steps, figures=self.figures))
+            if self.batch_env is not None:
+                self.batch_evaluation(model, n)
         return True

@@ -198,6 +198,7 @@ class G1HipEngine(EngineBase):
         cfg.num_envs, cfg.seed, cfg.auto_reset, cfg.device, cfg.max_ep_length = self.N, seed, int(auto_reset), device, max_ep_length
         cfg.task = int(task)
         cfg.pipeline = int(pipeline)        # 0 auto (split pipeline from 512 envs up), 1 monolithic, 2 split
+        self.auto_reset = bool(auto_reset)
         self.split = int(pipeline) == 2 or (int(pipeline) == 0 and self.N >= 512)      # the rule of dmg1_create (csrc/dm_g1.hip)
         self.task = int(task)
         self.obs_dim = NOBS_COMBINED if task else NOBS

@@ -16,7 +16,7 @@ import torch
 import torch.distributed as dist
 
 
-def main(argv=None):
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--algo", default="ppo", choices=["ppo", "sac"], help="sac: SB3 SAC of src/sac_sb3.py (one GPU, sac.py)")
     ap.add_argument("--buffer-size", type=int, default=5_000_000, help="--algo sac: replay transitions (src/sac_sb3.py)")
@@ -49,13 +49,35 @@ def main(argv=None):
     ap.add_argument("--rollout-graph", action="store_true", help="with --sub-batches > 1: capture the rollout as one hipGraph")
     ap.add_argument("--json", action="store_true", help="print a JSON throughput summary on rank 0")
     ap.add_argument("--eval-every", type=int, default=0, help="eval dashboard every N global steps (src/sb3_ppo.py:313 EVAL_N); 0 = off")
+    ap.add_argument("--eval-envs", type=int, default=0,
+                    help="> 0: batched deterministic evaluation (evaluation.py) on that many auto_reset=False envs on rank 0: at every "
+                         "--eval-every point (eval_batch.csv) and once after training (\"eval\" of the --json line); 0 = off")
     ap.add_argument("--run-name", default="run")
     ap.add_argument("--eval-dir", default="~/deep_mimic")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="gloo + several ranks on one GPU only rehearses the multi-rank path")
+    return ap
+
+
+def _eval_batch_env(args, motions, local_rank):
+    """The auto_reset=False twin of the training env with --eval-envs envs (one engine)."""
+    from .deepmimic_env import HipDeepMimicVecEnv
+    if args.env == "dp_combined_env":
+        from .combined_env import HipCombinedVecEnv
+        return HipCombinedVecEnv(args.eval_envs, robot=args.robot, device=local_rank, seed=4321, auto_reset=False)
+    if args.robot == "unitree_g1":
+        return HipDeepMimicVecEnv(args.eval_envs, motion=motions[0], robot="unitree_g1", device=local_rank, seed=4321, auto_reset=False)
+    return HipDeepMimicVecEnv(args.eval_envs, motion=motions if len(motions) > 1 else motions[0], device=local_rank, seed=4321,
+                              auto_reset=False)
+
+
+def main(argv=None):
+    ap = build_parser()
     args = ap.parse_args(argv)
     if args.bf16_learner and args.bf16x3_learner:
         ap.error("--bf16-learner and --bf16x3-learner are mutually exclusive")
+    if args.eval_envs < 0:
+        ap.error("--eval-envs must be >= 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if args.algo == "sac" and world > 1:
@@ -93,6 +115,7 @@ def main(argv=None):
               mlp_dtype=torch.bfloat16 if args.bf16_learner else "bf16x3" if args.bf16x3_learner else torch.float32)
     hist = []
     dash = None
+    batch_env = _eval_batch_env(args, motions, local_rank) if args.eval_envs > 0 and rank == 0 else None
     if args.eval_every > 0 and rank == 0:                               # src/sb3_ppo.py:273-313: one eval env next to the batch
         from .eval_dashboard import EvalDashboardCallback
         if args.env == "dp_combined_env":
@@ -101,7 +124,8 @@ def main(argv=None):
         else:
             from .deepmimic_env import DPEnv
             eval_env = DPEnv(motions[0], robot=args.robot, device=local_rank)
-        dash = EvalDashboardCallback(eval_env, args.motion + "_" + args.run_name, every_n_global_steps=args.eval_every, out_root=args.eval_dir)
+        dash = EvalDashboardCallback(eval_env, args.motion + "_" + args.run_name, every_n_global_steps=args.eval_every, out_root=args.eval_dir,
+                                     batch_env=batch_env)
 
     def _cb(p):
         hist.append(dict(p.stats, timesteps=p.num_timesteps * world))
@@ -115,6 +139,13 @@ def main(argv=None):
     if rank == 0:
         if args.save:
             ppo.save(os.path.expanduser(args.save))
+        final_eval = None
+        if batch_env is not None:                                       # the final policy, one deterministic episode per start frame
+            from .evaluation import evaluation_record
+            final_eval = evaluation_record(ppo, batch_env, ppo.num_timesteps * world)
+            if not args.json:
+                print("final evaluation: %(episodes)d episodes  ep_rew_mean %(ep_rew_mean).3f +- %(ep_rew_std).3f  ep_len_mean %(ep_len_mean).1f  "
+                      "reached the cap %(frac_reached_cap).2f" % final_eval, flush=True)
         if args.json:
             steady = hist[1:] if len(hist) > 1 else hist
             roll = sum(h["rollout_s"] for h in steady) / len(steady)
@@ -130,7 +161,10 @@ def main(argv=None):
                               "grad_allreduce_calls": ppo.grad_sync.calls,
                               "ep_rew_mean": hist[-1]["ep_rew_mean"], "ep_len_mean": hist[-1]["ep_len_mean"],
                               "explained_variance": hist[-1]["explained_variance"], "episodes": hist[-1]["episodes"],
-                              "curve": [(h["timesteps"], h["ep_rew_mean"], h["ep_len_mean"]) for h in hist[::max(1, len(hist) // 200)]]}))
+                              "curve": [(h["timesteps"], h["ep_rew_mean"], h["ep_len_mean"]) for h in hist[::max(1, len(hist) // 200)]],
+                              **({"eval": final_eval} if final_eval is not None else {})}))
+    if batch_env is not None:
+        batch_env.close()
     env.close()
     if world > 1:
         dist.destroy_process_group()
@@ -143,6 +177,7 @@ def _train_sac(args, env, motions, local_rank):
               learning_starts=args.learning_starts, gradient_steps=args.gradient_steps, seed=args.seed)
     hist = []
     dash = None
+    batch_env = _eval_batch_env(args, motions, local_rank) if args.eval_envs > 0 else None
     if args.eval_every > 0:
         from .eval_dashboard import EvalDashboardCallback
         if args.env == "dp_combined_env":
@@ -151,7 +186,8 @@ def _train_sac(args, env, motions, local_rank):
         else:
             from .deepmimic_env import DPEnv
             eval_env = DPEnv(motions[0], robot=args.robot, device=local_rank)
-        dash = EvalDashboardCallback(eval_env, args.motion + "_" + args.run_name, every_n_global_steps=args.eval_every, out_root=args.eval_dir)
+        dash = EvalDashboardCallback(eval_env, args.motion + "_" + args.run_name, every_n_global_steps=args.eval_every, out_root=args.eval_dir,
+                                     batch_env=batch_env)
 
     def _cb(m):
         hist.append(dict(m.stats))
@@ -168,6 +204,11 @@ def _train_sac(args, env, motions, local_rank):
     dt = time.perf_counter() - t0
     if args.save:
         sac.save(os.path.expanduser(args.save))
+    final_eval = None
+    if batch_env is not None:
+        from .evaluation import evaluation_record
+        final_eval = evaluation_record(sac, batch_env, sac.num_timesteps)
+        batch_env.close()
     if args.json:
         last = hist[-1] if hist else {}
         print(json.dumps({"workload": "sac", "envs": env.num_envs, "arch": args.arch, "buffer_size": args.buffer_size,
@@ -175,7 +216,8 @@ def _train_sac(args, env, motions, local_rank):
                           "env_steps_per_s": sac.num_timesteps / dt, "wall_s": dt,
                           "ep_rew_mean": last.get("ep_rew_mean"), "ep_len_mean": last.get("ep_len_mean"),
                           "critic_loss": last.get("critic_loss"), "actor_loss": last.get("actor_loss"), "ent_coef": last.get("ent_coef"),
-                          "curve": [(h["total_timesteps"], h["ep_rew_mean"]) for h in hist[::max(1, len(hist) // 200)]]}))
+                          "curve": [(h["total_timesteps"], h["ep_rew_mean"]) for h in hist[::max(1, len(hist) // 200)]],
+                          **({"eval": final_eval} if final_eval is not None else {})}))
     env.close()
 
 

@@ -191,6 +191,11 @@ class HipBatchEnv(_SB3VecEnv):
         if _SB3VecEnv is not object:  # pragma: no cover
             _SB3VecEnv.__init__(self, self.num_envs, self.observation_space, self.action_space)
 
+    @property
+    def auto_reset(self):
+        """What the engines were built with: ``True`` = SubprocVecEnv worker semantics (reset inside the step of a done env)."""
+        return bool(self.engine.auto_reset)
+
     # ---- zero-copy tensor API
     def reset_tensor(self, idx_init=None):
         for e, o, sl in zip(self.engines, self.sub_out, self.sub_slices):

@@ -123,6 +123,16 @@ int dm_reset(DmHandle h, const uint8_t *mask, const int32_t *idx_init, float *ob
 int dm_step(DmHandle h, const float *actions, float *obs, float *rew, uint8_t *done, float *terms,
             int32_t *reason, float *terminal_obs, void *stream);
 
+/* dm_step over a slot list, for runs in which envs drop out (evaluation.BatchEvaluator): slot s < nslots steps env env_ids[s]
+ * (device int32[>= nslots]); an entry < 0 ends that slot's wave at once, so a list padded with -1 may be launched with an nslots
+ * that is only an upper bound of the live entries.  No auto-reset, whatever DmConfig.auto_reset says: an env that is done keeps its
+ * terminal state, and an env that is not listed is not touched at all.  Inputs and outputs stay indexed by ENV (rows of envs not
+ * listed are left as they are).  The list's order is the launch order (DmConfig.lpt_schedule does not apply); the kernel variant is
+ * the one dm_step takes for the engine's num_envs, so an env's trajectory does not depend on how many others are still listed.
+ * 1 <= nslots <= num_envs.  terms and reason may be NULL. */
+int dm_step_active(DmHandle h, const float *actions, const int32_t *env_ids, int nslots, float *obs, float *rew, uint8_t *done,
+                   float *terms, int32_t *reason, void *stream);
+
 /* Replaces: `self.sim.step()` alone (deepmimic_env.py:362, frame_skip 1): ctrl <- actions, one mj_step-equivalent, state and
  * warm start advance; NO observation, reward, termination, counters or auto-reset.  The "physics-only" figure SURVEY 8(d)
  * asks for beside the full step(), and the building block of a frame_skip > 1 loop.  Envs are launched longest-first
@@ -309,6 +319,20 @@ long long dm_rollout_finish_workspace_bytes(int T, int N);
 int dm_rollout_finish(int T, int N, const float *rew, const void *done, int done_is_u8, const float *val, const float *last_val,
                       double gamma, double gae_lambda, float *adv, float *ret, float *ep_acc, float *ep_hist, unsigned *ep_count,
                       double *stats, void *work, long long work_bytes, void *stream);
+
+/* Episode bookkeeping of a batched evaluation, one launch (one workgroup) after every env step (csrc/dm_eval.hip).  Replaces the
+ * per-episode loop of stable_baselines3.common.evaluation.evaluate_policy [EXT] and of eval_dashboard_rollout (src/sb3_ppo.py:25-140):
+ * n envs run ONE episode each.  rew [n], done [n], reason [n], terms [n x terms_dim], obs [n x obs_dim] are the step's outputs, indexed
+ * by env.  For every env i with alive[i] != 0: ep_len[i] += 1; ep_ret[i] += rew[i] and ep_terms[i, :] += terms[i, :] in fp64, in step
+ * order (bit for bit a Python float loop over the fp32 rewards); if done[i]: ep_reason[i] = reason[i], last_obs[i, :] = obs[i, :],
+ * alive[i] = 0; else if ep_len[i] == max_steps: the same with ep_reason[i] = DM_EVAL_TRUNCATED.  Envs with alive[i] == 0 are neither
+ * read nor written (their step outputs are stale once they are no longer launched).  Then env_ids[0:c] = the envs still alive, ascending,
+ * env_ids[c:n] = -1, count[0] = c: the slot list of dm_step_active.  No atomics: the same list on every run.  Engine-agnostic (no
+ * handle; `device` is the HIP device ordinal of the buffers).  terms (with ep_terms), obs and last_obs may be NULL.  Any n >= 1. */
+#define DM_EVAL_TRUNCATED (-1)
+int dm_eval_advance(int n, int terms_dim, int max_steps, const float *rew, const uint8_t *done, const int32_t *reason,
+                    const float *terms, const float *obs, int obs_dim, uint8_t *alive, int32_t *ep_len, double *ep_ret,
+                    double *ep_terms, int32_t *ep_reason, float *last_obs, int32_t *env_ids, int32_t *count, int device, void *stream);
 
 /* The policy side of a rollout step as ONE launch (csrc/dm_policy.hip): both trunks of SB3's actor-critic MLP
  * (obs -> H1 -> H2 -> A / 1, tanh; what [EXT] ActorCriticPolicy.forward computes for src/sb3_ppo.py:307-313), the
