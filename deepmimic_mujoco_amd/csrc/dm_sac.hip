@@ -10,6 +10,12 @@
 //   ring unsigned[4]:    [0] write position (vec-env steps), [1] filled steps, [2] block ticket of dm_sac_store, [3] episodes done
 //   counter unsigned[1]: draw counter (rollout: bumped by dm_sac_store; learner: bumped by dm_sac_polyak)
 // Draws use the (seed, row, counter, index) hash of dm_policy_sample, so a test can restate every one of them.
+//
+// Precision of the squashed action.  a = tanh(u), u = mu + std eps, is held to 4 ulp of 1 against an fp64 evaluation
+// (tests/sac_kernels_ref64.py: A_TOL).  In fp32 that cannot be met: std reaches e^2, so an error of 4e-7 in eps (dm_normal2 forms
+// its angle as fl(2 pi) u2) is 3e-6 in u, and where std eps cancels a mu of 9 or 12 half an ulp of the product alone is A_TOL / 2.
+// So the noise and u are formed in fp64 from the same two uniforms as dm_normal2 (sac_normal2, sac_squash_u) and rounded once:
+// fl(u) is off by 2^-24 |u|, which tanh carries as (1 - a^2) |u| 2^-24 <= 0.45 x 2^-24, plus tanhf's 2 ulp.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -24,6 +30,20 @@ constexpr int SAC_EP_HIST = 100;            // SB3's ep_info_buffer: deque(maxle
 constexpr unsigned SAC_GATHER_TAG = 0xFFFF0000u;
 
 __device__ __forceinline__ float sac_clamp_ls(float ls) { return fminf(fmaxf(ls, -20.f), 2.f); }
+
+// dm_normal2's pair (csrc/dm_rng.h: the same hashes, u1 in (0, 1], u2 in [0, 1), cosine first) in fp64, the angle as 2 u2 half turns
+struct SacNormal2 { double e0, e1; };
+__device__ __forceinline__ SacNormal2 sac_normal2(uint64_t seed, uint32_t r, uint32_t ctr, uint32_t j) {
+  const double u1 = ((double)(dm_hash32(seed, r, ctr, j) >> 8) + 1.0) * (1.0 / 16777216.0);
+  const double u2 = (double)(dm_hash32(seed, r, ctr, j + 1u) >> 8) * (1.0 / 16777216.0);
+  const double rad = sqrt(-2.0 * log(u1));
+  double sn, cs;
+  sincospi(2.0 * u2, &sn, &cs);
+  return {rad * cs, rad * sn};
+}
+
+// u = mu + exp(ls) eps formed in fp64, rounded once (ls is the clamped log_std)
+__device__ __forceinline__ float sac_squash_u(float mu, float ls, double eps) { return (float)((double)mu + exp((double)ls) * eps); }
 
 // fixed-order block sum (256 threads): the same bits on every replay.  An LDS tree on purpose, not the wave butterfly of
 // ppo_block_sum (dm_ppo_common.h): the two add in different orders, so they are not to be merged.
@@ -47,8 +67,8 @@ __global__ void sac_act_kernel(const float *head, int N, int A, int ld, unsigned
   if (e >= N) return;
   const unsigned ctr = counter[0];
   for (int j = 0; j < A; j += 2) {
-    float eps[2] = {0.f, 0.f};
-    if (!warmup && !deterministic) { const DmNormal2 n = dm_normal2(seed, (unsigned)e, ctr, (unsigned)j); eps[0] = n.e0; eps[1] = n.e1; }
+    double eps[2] = {0.0, 0.0};
+    if (!warmup && !deterministic) { const SacNormal2 n = sac_normal2(seed, (unsigned)e, ctr, (unsigned)j); eps[0] = n.e0; eps[1] = n.e1; }
     for (int q = 0; q < 2 && j + q < A; q++) {
       const int c = j + q;
       const float l = lo[c], h = hi[c];
@@ -59,7 +79,7 @@ __global__ void sac_act_kernel(const float *head, int N, int A, int ld, unsigned
         a = 2.f * ((ae - l) / (h - l)) - 1.f;
       } else {
         const float mu = head[(size_t)e * ld + c];
-        a = deterministic ? tanhf(mu) : tanhf(mu + expf(sac_clamp_ls(head[(size_t)e * ld + A + c])) * eps[q]);
+        a = deterministic ? tanhf(mu) : tanhf(sac_squash_u(mu, sac_clamp_ls(head[(size_t)e * ld + A + c]), eps[q]));
         ae = l + 0.5f * (a + 1.f) * (h - l);
       }
       act[(size_t)e * A + c] = a;
@@ -158,14 +178,14 @@ __global__ void __launch_bounds__(SAC_THREADS) sac_head_fwd_kernel(const float *
     float lp = 0.f;
     float *dst = r < Rpi ? a_pi + (size_t)r * lda : a_next + (size_t)(r - Rpi) * lda;
     for (int j = 0; j < A; j += 2) {
-      const DmNormal2 n = dm_normal2(seed, (unsigned)r, ctr, (unsigned)j);
-      const float eps[2] = {n.e0, n.e1};
+      const SacNormal2 n = sac_normal2(seed, (unsigned)r, ctr, (unsigned)j);
+      const double eps[2] = {n.e0, n.e1};
       for (int q = 0; q < 2 && j + q < A; q++) {
         const int c = j + q;
         const float mu = head[(size_t)r * 2 * A + c], ls = sac_clamp_ls(head[(size_t)r * 2 * A + A + c]);
-        const float a = tanhf(mu + expf(ls) * eps[q]);
+        const float a = tanhf(sac_squash_u(mu, ls, eps[q])), e = (float)eps[q];
         dst[c] = a;
-        lp += -0.5f * eps[q] * eps[q] - ls - 0.9189385332046727f - logf(1.f - a * a + 1e-6f);
+        lp += -0.5f * e * e - ls - 0.9189385332046727f - logf(1.f - a * a + 1e-6f);
       }
     }
     logp[r] = lp;
@@ -242,17 +262,17 @@ __global__ void __launch_bounds__(SAC_THREADS) sac_head_bwd_kernel(const float *
   const float w = st[4] / (float)B;
   for (int r = threadIdx.x; r < B; r += SAC_THREADS) {
     for (int j = 0; j < A; j += 2) {
-      const DmNormal2 n = dm_normal2(seed, (unsigned)r, ctr, (unsigned)j);
-      const float eps[2] = {n.e0, n.e1};
+      const SacNormal2 n = sac_normal2(seed, (unsigned)r, ctr, (unsigned)j);
+      const double eps[2] = {n.e0, n.e1};
       for (int q = 0; q < 2 && j + q < A; q++) {
         const int c = j + q;
         const float mu = head[(size_t)r * 2 * A + c], lsr = head[(size_t)r * 2 * A + A + c], ls = sac_clamp_ls(lsr);
-        const float sd = expf(ls), a = tanhf(mu + sd * eps[q]);
+        const float sd = expf(ls), a = tanhf(sac_squash_u(mu, ls, eps[q])), e = (float)eps[q];
         const float da = dx[(size_t)r * K + col + c] + dx[(size_t)(B + r) * K + col + c];
         const float om = 1.f - a * a;
         const float gu = da * om + w * 2.f * a * om / (om + 1e-6f);
         dhead[(size_t)r * 2 * A + c] = gu;
-        dhead[(size_t)r * 2 * A + A + c] = (lsr >= -20.f && lsr <= 2.f) ? gu * sd * eps[q] - w : 0.f;
+        dhead[(size_t)r * 2 * A + A + c] = (lsr >= -20.f && lsr <= 2.f) ? gu * sd * e - w : 0.f;
       }
     }
   }

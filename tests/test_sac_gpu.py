@@ -11,7 +11,12 @@ from sac_helpers import BanditEnv, gather_rows, named_actor, named_critic, norma
 pytestmark = pytest.mark.gpu
 
 SHAPES = [(67, 28, (256, 128)), (67, 28, (1024, 512)), (98, 23, (256, 128)), (98, 23, (1024, 512))]
-B = 256
+# (D, A, arch, batch size, envs): the four nets at SB3's batch of 256 (one full pass of the 256-thread heads), and a batch of 100
+# on 7 envs with hidden widths 96 and 40, where every one-workgroup loop ends in a partial pass and both layers straddle the
+# 64-column tiles of the first-layer and ReLU-backward kernels
+RAGGED = (5, 3, (96, 40), 100, 7)
+STEP_CASES = [pytest.param(*s, 256, 64, id="%d-%d-arch%d" % (s[0], s[1], i)) for i, s in enumerate(SHAPES)] + \
+             [pytest.param(*RAGGED, id="5-3-arch4-b100-n7")]
 # Tolerance basis.  fp32 rounds at 6e-8; a dot product of <= 1024 terms carries ~sqrt(1024) x 6e-8 = 2e-6 relative error and a
 # gradient passes through at most six of them (critic forward, backward into the action, head, actor backward): ~1e-5.  A
 # handful of ReLU units whose pre-activation lies within that error of 0 switch between fp32 and fp64 and move a gradient by
@@ -21,11 +26,11 @@ B = 256
 GRAD_TOL, PARAM_TOL, HEAD_TOL = 1e-3, 1e-4, 1e-4
 
 
-def _sac(D, A, arch, n=64, steps=8, done_every=3, **kw):
+def _sac(D, A, arch, B=256, n=64, steps=8, done_every=3, **kw):
     from deepmimic_mujoco_amd.sac import SAC
     torch.manual_seed(0)
     env = BanditEnv(n, D, A, device="cuda", seed=3, done_every=done_every)
-    sac = SAC(env, net_arch=arch, batch_size=kw.pop("batch_size", B), learning_starts=kw.pop("learning_starts", 10 ** 9), seed=1,
+    sac = SAC(env, net_arch=arch, batch_size=B, learning_starts=kw.pop("learning_starts", 10 ** 9), seed=1,
               device="cuda", **kw)
     for _ in range(steps):
         sac.env_step()
@@ -37,15 +42,15 @@ def _per_tensor(got, want, tol, what):
         assert rel_l2(got[k], want[k]) < tol, (what, k, rel_l2(got[k], want[k]))
 
 
-@pytest.mark.parametrize("D,A,arch", SHAPES)
-def test_fused_gradient_steps_match_fp64(D, A, arch):
+@pytest.mark.parametrize("D,A,arch,B,n", STEP_CASES)
+def test_fused_gradient_steps_match_fp64(D, A, arch, B, n):
     """Three fused gradient steps from a state where every part of the update shows: the target critics differ from the online
     ones, alpha = 0.2, a third of the transitions are not terminal (the target network enters y), Adam is past its first step
     after the first compared step, and one log_std output sits below the clamp.  Before each step the fp64 reference takes the
     learner's state (weights, targets, Adam moments and step count, log_ent_coef), so each step is compared on its own, per
     tensor, with its rows and noise restated from the hash for that counter value."""
-    env, sac = _sac(D, A, arch)
-    n = sac.n_envs
+    env, sac = _sac(D, A, arch, B, n)
+    assert sac.n_envs == n and sac.batch_size == B
     g = torch.Generator(device="cuda").manual_seed(11)
     with torch.no_grad():
         sac.critic_target.add_(0.3 * sac.critic.abs() * torch.randn(sac.critic.shape, device="cuda", generator=g))
@@ -150,9 +155,9 @@ def test_ring_wraps_on_device():
     assert sac.ring_state.tolist()[:3] == [7 % 3, 3, 0]
 
 
-@pytest.mark.parametrize("D,A,arch", [SHAPES[1]])
-def test_graph_replay_is_bit_identical_to_eager(D, A, arch):
-    env, sac = _sac(D, A, arch)
+@pytest.mark.parametrize("D,A,arch,B,n", [pytest.param(*SHAPES[1], 256, 64, id="67-28-arch0"), pytest.param(*RAGGED, id="5-3-arch1-b100-n7")])
+def test_graph_replay_is_bit_identical_to_eager(D, A, arch, B, n):
+    env, sac = _sac(D, A, arch, B, n)
     snap = [t.clone() for t in sac.state_tensors()]
     for _ in range(3):
         sac.gradient_step_fused()
