@@ -2421,6 +2421,9 @@ __device__ __forceinline__ bool task_and_finish(const Launch &P, const Dev &T, c
         }
         X.ep_rew += X.reward;
         X.ep_len += 1;
+        // :465 reads `np.max(obs) > 100 or np.min(obs) < -100`, which a NaN passes (the oracle restates it literally).  Written
+        // here as "not inside the bound" ON PURPOSE, so that a NaN ends the episode with zeros like any other divergence instead of
+        // reaching the policy; with finite values the two agree, and mj_checkPos / Vel / Acc catch a NaN state before this line.
         const bool ob = !(fabsf(obs_a) <= P.obs_bound) || !(fabsf(obs_b) <= P.obs_bound);
         if (__any(ob)) {
           obs_a = 0; obs_b = 0; X.reward = 0; X.done = true; X.reason = 6;

@@ -1331,7 +1331,10 @@ int dmo_env_step(const DmModel *m, DmoData *d, DmoEnv *e, const DmoClip *clip, c
   e->idx_curr = (e->idx_curr + 1) % clip->L;                      /* :452 */
   e->episode_reward += *reward;
   e->episode_length += 1;
-  for (int i = 0; i < DM_NOBS; i++)                               /* :465-476 */
+  /* :465-476.  As the reference writes it: a NaN passes both comparisons.  The HIP engines test !(|obs| <= bound) instead, so
+   * that a NaN ends the episode with zeros; that difference is deliberate (csrc/dm_g1.hip, task_and_finish) and no test case
+   * depends on it: NaN states are caught by mj_checkPos / Vel / Acc first. */
+  for (int i = 0; i < DM_NOBS; i++)
     if (obs[i] > 100.0 || obs[i] < -100.0) {
       memset(obs, 0, sizeof(double) * DM_NOBS);
       memset(terms, 0, sizeof(double) * 5);
