@@ -93,16 +93,37 @@ __device__ __forceinline__ int lane_sel_i(int a, int b) {
   asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(out) : "v"(b), "v"(a), "s"(MASK));
   return out;
 }
-// Column elimination step for dof K: walk the static ancestor chain I = parent(K), parent(parent(K)), ...
-template <int K, int I>
-struct ElimAnc {
-  static __device__ __forceinline__ void run(float (&C)[DMK_NV], const float Cs) {
-    if constexpr (I >= 0) {
-      C[I] = fmaf(-rl(Cs, I), C[K], C[I]);
-      ElimAnc<K, (I >= 0 ? topo::PARENT[I >= 0 ? I : 0] : -1)>::run(C, Cs);
-    }
-  }
-};
+// Column elimination C[i] -= C[k] M[k][i] / M[k][k] over the dof tree, emitted in the order of topo::FACTOR_SCHED: a
+// topological order of the descending-k loop's dependency DAG (every C[i] gets the same FMAs in the same order, every
+// pivot reads the same C[k]: the bits do not change) in which the limbs run side by side and a batch of broadcasts stands
+// in front of its FMAs.  The empty asm pins the batch's scalars in distinct SGPRs at one point; without it each
+// v_readlane is paired with its FMA through one SGPR and pays the two wait states of the VALU-SGPR hazard in an s_nop.
+template <int N>
+__device__ __forceinline__ void sgpr_batch(float (&a)[topo::FS_SLOTS]) {
+  static_assert(N >= 1 && N <= 8 && topo::FS_SLOTS == 8, "one asm statement per batch size");
+  if constexpr (N == 1) asm("" : "+s"(a[0]));
+  if constexpr (N == 2) asm("" : "+s"(a[0]), "+s"(a[1]));
+  if constexpr (N == 3) asm("" : "+s"(a[0]), "+s"(a[1]), "+s"(a[2]));
+  if constexpr (N == 4) asm("" : "+s"(a[0]), "+s"(a[1]), "+s"(a[2]), "+s"(a[3]));
+  if constexpr (N == 5) asm("" : "+s"(a[0]), "+s"(a[1]), "+s"(a[2]), "+s"(a[3]), "+s"(a[4]));
+  if constexpr (N == 6) asm("" : "+s"(a[0]), "+s"(a[1]), "+s"(a[2]), "+s"(a[3]), "+s"(a[4]), "+s"(a[5]));
+  if constexpr (N == 7) asm("" : "+s"(a[0]), "+s"(a[1]), "+s"(a[2]), "+s"(a[3]), "+s"(a[4]), "+s"(a[5]), "+s"(a[6]));
+  if constexpr (N == 8) asm("" : "+s"(a[0]), "+s"(a[1]), "+s"(a[2]), "+s"(a[3]), "+s"(a[4]), "+s"(a[5]), "+s"(a[6]), "+s"(a[7]));
+}
+__device__ __forceinline__ void factor_columns(float (&C)[DMK_NV]) {
+  float d[topo::FS_SLOTS], m[topo::FS_SLOTS], rk[DMK_NV], Cs[DMK_NV];
+  StaticFor<0, topo::FS_NOPS>::run([&](auto nc) {
+    constexpr topo::FactorOp o = topo::FACTOR_SCHED[decltype(nc)::value];
+    if constexpr (o.op == topo::FS_DIAG) d[o.slot] = rl(C[o.k], o.k);
+    if constexpr (o.op == topo::FS_RCP) rk[o.k] = __builtin_amdgcn_rcpf(d[o.slot]);
+    if constexpr (o.op == topo::FS_SCALE) Cs[o.k] = C[o.k] * rk[o.k];
+    if constexpr (o.op == topo::FS_BCAST) m[o.slot] = rl(Cs[o.k], o.i);
+    if constexpr (o.op == topo::FS_FMA) C[o.i] = fmaf(-m[o.slot], C[o.k], C[o.i]);
+    if constexpr (o.op == topo::FS_FENCE) sgpr_batch<o.slot>(m);
+    if constexpr (o.op == topo::FS_DFENCE) sgpr_batch<o.slot>(d);
+    return true;
+  });
+}
 // Triangular solves with the published sparse factor (lane = dof, rows UNSCALED: L[i][j] = M[i][j] * dinv[i]).
 // The broadcast value comes from a static lane, the factor entry from a per-lane base plus a static offset, and the
 // set of lanes a step touches is a compile-time lane mask: 5 instructions per step.
@@ -777,14 +798,8 @@ __device__ __forceinline__ float fwd_smooth(GDev &T, const int lane, const float
   // ---- L^T D L on the columns: eliminate dof k = 33..1.  M[k][k] and the multipliers M[k][i] / M[k][k] of the
   // ancestors i of k are broadcast from static lanes with v_readlane; every lane applies
   // C[i] -= C[k] * M[k][i] / M[k][k] to the registers of the ancestors i — lanes outside the ancestor set of k hold
-  // C[k] = 0, so no predicate is needed.  2 VALU per (k, ancestor) pair, 276 pairs.
-  StaticFor<0, DMK_NV - 1>::run([&](auto ic) {
-    constexpr int k = DMK_NV - 1 - decltype(ic)::value;   // 33 .. 1
-    const float rk = __builtin_amdgcn_rcpf(rl(C[k], k));
-    const float Cs = C[k] * rk;
-    ElimAnc<k, topo::PARENT[k]>::run(C, Cs);
-    return true;
-  });
+  // C[k] = 0, so no predicate is needed.  2 VALU per (k, ancestor) pair, 276 pairs, in the order of topo::FACTOR_SCHED.
+  factor_columns(C);
   // publish the factor in the sparse MuJoCo layout (row k: M(k,k), M(k,parent), ...), rows UNSCALED:
   // L[i][j] = M[i][j] * dinv[i] is applied by the users.  Lane j owns M[k][j] at S.M[MADR[k] + NANC[k] - depth_j];
   // lanes outside the ancestor set of k write to a spare slot.
