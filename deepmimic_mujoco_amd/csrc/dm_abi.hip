@@ -164,6 +164,7 @@ static void build_tables(const DmModel &m, DmDev &T) {
   int p = 0;
   for (int b = 0; b < DMK_MAXANC; b++)
     for (int a = 0; a <= b; a++) { T.tri_a[p] = (uint8_t)a; T.tri_b[p] = (uint8_t)b; p++; }
+  dm_build_lane_records(T);   // T.rec: the per-lane copies the step kernels load a phase ahead (dm_tables.h)
 }
 
 static int check_model(DmEngine *e, const DmModel &m) {

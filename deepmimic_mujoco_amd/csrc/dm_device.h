@@ -13,6 +13,7 @@
 #include <stdint.h>
 
 #include "../../include/dm_model.h"
+#include "dm_tables.h"   // DmDev, DmPairDev, the lane-major records (host-buildable, no HIP)
 
 #define DMK_NQ DM_NQ
 #define DMK_NV DM_NV
@@ -24,55 +25,8 @@
 #define DMK_LANEROW 64         // one row per lane up to here; 65..128 rows take the two-rows-per-lane path
 #define DMK_REGROW 32          // A-matrix columns kept in registers; columns 32..63 spill to ar_scratch
 #define DMK_MSTRIDE 35         // dense tree-sparse M, odd stride: conflict-free rows and columns
-#define DMK_MAXANC 12          // deepest dof has 12 ancestors (root 6 + hip 3 + knee 1 + ankle x,y)
 #define DMK_STATE_STRIDE 144   // floats per env in the HBM state row (see DmState)
 #define DMK_CLIP_ROW 80        // floats per clip frame row (73 used)
-
-// One collision candidate: everything the prefilter and the narrowphase need except the poses.
-struct DmPairDev {
-  int16_t g1, g2;
-  int8_t t1, t2, pad0, pad1;
-  float margin, rbsum;   // max of the two margins; sum of the bounding radii (plane: radius of geom 2)
-  float z1[3], z2[3];    // geom sizes
-};
-
-// Global-memory (read-only) model tables, fp32.  Built on the host from DmModel.
-struct DmDev {
-  // scalars
-  float timestep, tolerance, pgs_scale, gravity[3];
-  float K, B;               // reference-acceleration stiffness / damping (refsafe applied)
-  float solimp[5];
-  float total_mass_inv;
-  float qpos0[36];
-  int32_t iterations, npair;
-  int32_t torso_body, rfoot_geom, lfoot_geom, floor_geom;
-  int32_t ee_geom[4];
-  // bodies
-  int32_t b_parent[16], b_depth[16], b_dofadr[16], b_dofnum[16];
-  float b_pos[16][3], b_ipos[16][3], b_inertia[16][6], b_mass[16], b_invw[16];
-  uint32_t b_subtree[16];       // bit c: body c is in the subtree of b (incl. b)
-  uint64_t b_chain[16];         // bit k: dof k moves body b
-  uint32_t b_chainb[16];        // ancestor bodies root..self, one byte each (0 = none)
-  // dofs
-  int32_t d_body[DM_NV], d_nanc[DM_NV], d_act[DM_NV], d_limited[DM_NV];
-  float d_axis[DM_NV][3];       // joint axis in the body frame (hinges)
-  float d_arm[DM_NV], d_damp[DM_NV], d_invw[DM_NV], d_lo[DM_NV], d_hi[DM_NV];
-  float d_gear[DM_NV], d_clo[DM_NV], d_chi[DM_NV];
-  uint8_t d_anc[DM_NV][DMK_MAXANC];
-  uint8_t d_ancabs[DM_NV][DMK_MAXANC + 4]; // ancestor dof at absolute depth d (0 if none)
-  uint64_t d_desc[DM_NV];       // bit k: dof k is a strict descendant
-  int32_t d_pbody[DM_NV];       // parent body of the dof's body
-  uint64_t nanc_pack[3];        // d_nanc of every dof, 4 bits each
-  uint64_t d_ancm[DM_NV];       // bit j: dof j is a strict ancestor
-  int32_t d_madr[DM_NV];        // start of row i in the sparse factor
-  // geoms
-  int32_t g_body[16], g_type[16], g_condim[16];
-  float g_pos[16][3], g_mat[16][9], g_size[16][3], g_rbound[16], g_margin[16], g_mu[16];
-  // candidate pairs (canonical order)
-  int16_t p_g1[DM_MAXPAIR], p_g2[DM_MAXPAIR];
-  DmPairDev pairs[DM_MAXPAIR];
-  uint8_t tri_a[80], tri_b[80]; // lower-triangle pair decode for the factorisation
-};
 
 // Per-env LDS working set (one wave).  13 008 B: twelve waves per CU (three per SIMD) need <= 13 653 B each.
 struct EnvLds {

@@ -59,6 +59,17 @@ typedef float mfma_f16v __attribute__((ext_vector_type(16)));
 #endif
 typedef const __attribute__((address_space(1))) DmDev GDev;          // model tables: global address space
 typedef const __attribute__((address_space(1))) DmPairDev GPair;
+// One 16-byte chunk of a lane-major record (dm_tables.h): REC4(T, body, lane, c) is one global_load_dwordx4 at
+// base + lane * stride + 16 c, the base in SGPRs and the 32-bit offset in one VGPR (a 64-bit per-lane pointer would stay
+// live from the first request of a stage to the last).  A phase's chunks are requested one phase ahead and carried across
+// the SYNC() in registers.
+typedef uint32_t rec_u4 __attribute__((ext_vector_type(4)));
+typedef const __attribute__((address_space(1))) rec_u4 GRec4;
+typedef const __attribute__((address_space(1))) char GByte;
+#define REC4(T, role, idx, c)                                                                                    \
+  (*(GRec4 *)((GByte *)&(T) + ((unsigned)(offsetof(DmDev, rec) + offsetof(DmLaneRec, role) + 16 * (c)) +         \
+                               (unsigned)(idx) * (unsigned)sizeof(((DmLaneRec *)nullptr)->role[0]))))
+#define RECF(x) __uint_as_float(x)
 #define MINVALF 1e-15f
 #define MAXVALF 1e10f
 
@@ -572,15 +583,16 @@ __device__ __forceinline__ float fwd_smooth(GDev &T, const int lane, const float
   const int lk = lane < DMK_NV ? lane : 0;       // lane as dof
   const int lg = lane < DMK_NG ? lane : 0;       // lane as geom
   const bool isbody = lane >= 1 && lane < DMK_NB, isdof = lane < DMK_NV;
-  // role constants of this phase (function-local registers)
-  const float bmass = (lane < DMK_NB) ? T.b_mass[lb] : 0.f;
-  const int b_dofadr = T.b_dofadr[lb], b_dofnum = T.b_dofnum[lb];
-  const uint32_t b_chain4 = T.b_chainb[lb];      // ancestor bodies root..self, one byte each (0 = none)
-  const unsigned b_sub = T.b_subtree[lb];
-  const int d_body = T.d_body[lk], d_nanc = T.d_nanc[lk], d_pbody = T.d_pbody[lk];
+  // role constants come from the lane-major records (T.rec, indexed by the lane itself: lanes past a role's count hold
+  // entry 0), each phase's chunks requested one phase ahead.  Here: what P1 and P2 need of the body, and the dof's ids.
+  const rec_u4 rd0 = REC4(T, dof, lane, 0);                        // body, nanc, pbody (arm: see armv below)
+  const int d_body = (int)rd0.x, d_nanc = (int)rd0.y, d_pbody = (int)rd0.z;
   const float mtot_inv = T.total_mass_inv;
 
   if constexpr (!DAMP2) {
+  const rec_u4 rb0 = REC4(T, body, lane, 0), rb1 = REC4(T, body, lane, 1), rb2 = REC4(T, body, lane, 2),
+               rb3 = REC4(T, body, lane, 3), rb4 = REC4(T, body, lane, 4);
+  const float bmass = (lane < DMK_NB) ? RECF(rb1.w) : 0.f;
   // ---- P0: normalise the free-joint quaternion in place (mj_kinematics does); half-angle sin/cos
   {
     float q[4] = {S.qpos[3], S.qpos[4], S.qpos[5], S.qpos[6]};
@@ -603,17 +615,17 @@ __device__ __forceinline__ float fwd_smooth(GDev &T, const int lane, const float
       for (int i = 0; i < 4; i++) q[i] = S.qpos[3 + i];
     } else {
       {  // first hinge: q is still the identity (spelled out: without fast-math hipcc keeps the 0 * x products)
-        const int k = b_dofadr;
-        const float al[3] = {T.d_axis[k][0], T.d_axis[k][1], T.d_axis[k][2]};
+        const int k = (int)rb0.x;
+        const float al[3] = {RECF(rb2.x), RECF(rb2.y), RECF(rb2.z)};
         S.xaxis[k][0] = al[0]; S.xaxis[k][1] = al[1]; S.xaxis[k][2] = al[2];       // parent-frame axis for now
         const float c = S.cs[k][0], sn = S.cs[k][1];
         q[0] = c; q[1] = al[0] * sn; q[2] = al[1] * sn; q[3] = al[2] * sn;
       }
 #pragma unroll
       for (int j = 1; j < 3; j++) {
-        if (j < b_dofnum) {
-          const int k = b_dofadr + j;
-          const float al[3] = {T.d_axis[k][0], T.d_axis[k][1], T.d_axis[k][2]};
+        if (j < (int)rb0.y) {
+          const int k = (int)rb0.x + j;
+          const float al[3] = {RECF(j == 1 ? rb2.w : rb3.z), RECF(j == 1 ? rb3.x : rb3.w), RECF(j == 1 ? rb3.y : rb4.x)};
           float ax[3], ql[4], qn[4];
           quat_rot(ax, q, al);
           S.xaxis[k][0] = ax[0]; S.xaxis[k][1] = ax[1]; S.xaxis[k][2] = ax[2];   // parent-frame axis for now
@@ -625,9 +637,13 @@ __device__ __forceinline__ float fwd_smooth(GDev &T, const int lane, const float
       }
     }
     for (int i = 0; i < 4; i++) S.u.v.qloc[lb][i] = q[i];
-    for (int i = 0; i < 3; i++) S.u.v.qloc[lb][4 + i] = (lb == 1) ? S.qpos[i] : T.b_pos[lb][i];
+    for (int i = 0; i < 3; i++) S.u.v.qloc[lb][4 + i] = (lb == 1) ? S.qpos[i] : RECF(rb1[i]);
   }
   SYNC();
+  // requested in front of P2's arithmetic: the body's inertia (cinert) and the lane's geom (P3)
+  const rec_u4 rb5 = REC4(T, body, lane, 5), rb6 = REC4(T, body, lane, 6);
+  const rec_u4 rg0 = REC4(T, geom, lane, 0), rg1 = REC4(T, geom, lane, 1), rg2 = REC4(T, geom, lane, 2), rg3 = REC4(T, geom, lane, 3);
+  const uint32_t b_chain4 = rb0.z;               // ancestor bodies root..self, one byte each (0 = none)
   // ---- P2 (lane = body): compose along the ancestor chain root -> self
   if (isbody) {
     // the chain always starts at the root body (byte 0 of b_chainb = 1): start from its local pose
@@ -650,7 +666,7 @@ __device__ __forceinline__ float fwd_smooth(GDev &T, const int lane, const float
     quat_normalize(q);
     float m9[9], tv[3];
     quat2mat(m9, q);
-    const float ip[3] = {T.b_ipos[lb][0], T.b_ipos[lb][1], T.b_ipos[lb][2]};
+    const float ip[3] = {RECF(rb4.y), RECF(rb4.z), RECF(rb4.w)};
     mat_vec(tv, m9, ip);
     for (int i = 0; i < 3; i++) { S.xpos[lb][i] = pos[i]; S.xipos[lb][i] = pos[i] + tv[i]; }
     for (int i = 0; i < 4; i++) S.xquat[lb][i] = q[i];
@@ -670,9 +686,11 @@ __device__ __forceinline__ float fwd_smooth(GDev &T, const int lane, const float
       ax[0] = S.xmat[1][lane - 3]; ax[1] = S.xmat[1][3 + lane - 3]; ax[2] = S.xmat[1][6 + lane - 3];
     }
     if (lane < DMK_NG) {
-      const int gb = T.g_body[lg];
-      float bm[9], tv[3], gl[3] = {T.g_pos[lg][0], T.g_pos[lg][1], T.g_pos[lg][2]}, gm[9];
-      for (int i = 0; i < 9; i++) { bm[i] = S.xmat[gb][i]; gm[i] = T.g_mat[lg][i]; }
+      const int gb = (int)rg0.w;
+      const float gl[3] = {RECF(rg0.x), RECF(rg0.y), RECF(rg0.z)};
+      const float gm[9] = {RECF(rg1.x), RECF(rg1.y), RECF(rg1.z), RECF(rg1.w), RECF(rg2.x), RECF(rg2.y), RECF(rg2.z), RECF(rg2.w), RECF(rg3.x)};
+      float bm[9], tv[3];
+      for (int i = 0; i < 9; i++) bm[i] = S.xmat[gb][i];
       mat_vec(tv, bm, gl);
       for (int i = 0; i < 3; i++) S.gpos[lg][i] = S.xpos[gb][i] + tv[i];
       for (int i = 0; i < 3; i++)
@@ -703,7 +721,7 @@ __device__ __forceinline__ float fwd_smooth(GDev &T, const int lane, const float
   if (isbody) {
     float R[9], Tm[9], W[6], bi[6];
     for (int i = 0; i < 9; i++) R[i] = S.xmat[lb][i];
-    for (int i = 0; i < 6; i++) bi[i] = T.b_inertia[lb][i];
+    bi[0] = RECF(rb5.x); bi[1] = RECF(rb5.y); bi[2] = RECF(rb5.z); bi[3] = RECF(rb5.w); bi[4] = RECF(rb6.x); bi[5] = RECF(rb6.y);
     const float Ib[9] = {bi[0], bi[3], bi[4], bi[3], bi[1], bi[5], bi[4], bi[5], bi[2]};
     for (int i = 0; i < 3; i++)
       for (int j = 0; j < 3; j++) Tm[3 * i + j] = R[3 * i] * Ib[j] + R[3 * i + 1] * Ib[3 + j] + R[3 * i + 2] * Ib[6 + j];
@@ -758,7 +776,9 @@ __device__ __forceinline__ float fwd_smooth(GDev &T, const int lane, const float
       for (int i = 0; i < 6; i++) S.u.v.mbuf[lk][i] = buf[i];
     }
     SYNC();
-    const float armv = isdof ? (DAMP2 ? fmaf(T.timestep, T.d_damp[lk], T.d_arm[lk]) : T.d_arm[lk]) : 0.f;
+    // (the armature stays a load at its use: carried from the top of the function in rd0.w it cost dm_step_combined_kernel_w3
+    // spilled VGPRs, 90 against the 89 it had: DESIGN §3)
+    const float armv = isdof ? (DAMP2 ? fmaf(T.timestep, RECF(REC4(T, dof, lane, 1).z), T.d_arm[lk]) : T.d_arm[lk]) : 0.f;
     // dots[k] = cdof_lane . buf_k.  k < 32 on the matrix pipe (32 x 32 x 6: operand A = buf from LDS, operand B = the
     // lanes' cdof with the odd components swapped into the upper half-wave; dof lanes 32, 33 only own rows 32, 33);
     // k = 32, 33 with FMAs.
@@ -800,6 +820,9 @@ __device__ __forceinline__ float fwd_smooth(GDev &T, const int lane, const float
   // C[i] -= C[k] * M[k][i] / M[k][k] to the registers of the ancestors i — lanes outside the ancestor set of k hold
   // C[k] = 0, so no predicate is needed.  2 VALU per (k, ancestor) pair, 276 pairs, in the order of topo::FACTOR_SCHED.
   factor_columns(C);
+  // requested in front of the publication: what the velocity stage and qacc_smooth need (the body's dof range and chain
+  // again, so that they are not held across the factorisation; the dof's factor row, actuator and damping)
+  const rec_u4 rv0 = REC4(T, body, lane, 0), rd1 = REC4(T, dof, lane, 1), rd2 = REC4(T, dof, lane, 2);
   // publish the factor in the sparse MuJoCo layout (row k: M(k,k), M(k,parent), ...), rows UNSCALED:
   // L[i][j] = M[i][j] * dinv[i] is applied by the users.  Lane j owns M[k][j] at S.M[MADR[k] + NANC[k] - depth_j];
   // lanes outside the ancestor set of k write to a spare slot.
@@ -815,10 +838,9 @@ __device__ __forceinline__ float fwd_smooth(GDev &T, const int lane, const float
   }
   SYNC();
   float dv = 0.f;
-  const int mrow = T.d_madr[lk] + d_nanc;          // S.M[mrow - depth(j)] = M[lane][j]
-  const uint64_t ancm = T.d_ancm[lk];              // bit j: dof j is a strict ancestor of this lane's dof
+  const int mrow = (int)rd1.x + d_nanc;            // S.M[mrow - depth(j)] = M[lane][j]
   if (isdof) {
-    const float Md = S.M[T.d_madr[lk]];
+    const float Md = S.M[(int)rd1.x];
     dv = 1.0f / Md;
     S.dinv[lk] = dv;
     S.dsqrtinv[lk] = 1.0f / sqrtf(Md);
@@ -830,6 +852,8 @@ __device__ __forceinline__ float fwd_smooth(GDev &T, const int lane, const float
     xs = isdof ? rhs : 0.f;
   } else {
   // ---- velocity stage, lane-parallel.  Pass A (lane = body): w_b = sum over the body's dofs of cdof * qvel
+  const int b_dofadr = (int)rv0.x, b_dofnum = (int)rv0.y;
+  const uint32_t b_chain4 = rv0.z;
   if (isbody) {
     float w[6] = {0, 0, 0, 0, 0, 0};
     const int nd = (lb == 1) ? 6 : b_dofnum;
@@ -922,9 +946,9 @@ __device__ __forceinline__ float fwd_smooth(GDev &T, const int lane, const float
     float bias = 0;
     for (int i = 0; i < 6; i++) bias += S.cdof[lk][i] * S.u.v.cacc[d_body][i];
     float act = 0;
-    const int da = T.d_act[lk];
-    if (da >= 0) act = T.d_gear[lk] * clampf(S.ctrl[da], T.d_clo[lk], T.d_chi[lk]);
-    xs = -T.d_damp[lk] * S.qvel[lk] - bias + act;
+    const int da = (int)rd1.y;
+    if (da >= 0) act = RECF(rd1.w) * clampf(S.ctrl[da], RECF(rd2.x), RECF(rd2.y));
+    xs = -RECF(rd1.z) * S.qvel[lk] - bias + act;
   }
   }  // !DAMP2
   xs = solve_LT(xs, dv, -d_nanc_s, g_S.M);
@@ -1193,19 +1217,40 @@ __device__ __forceinline__ void build_row(GDev &T, EnvLds &S, const int r, const
           lsign = (v & 1) ? -1.f : 1.f;
           rtype = 0;
           float q = S.qpos[ldof + 1];
-          rpos = (v & 1) ? (T.d_hi[ldof] - q) : (q - T.d_lo[ldof]);
+          float lo, hi;
+          if constexpr (PF) {   // the limit-row record of the dof: three words of one 16-byte record (as one 16-byte load: more scratch)
+            lo = T.rec.lrow[ldof].lo; hi = T.rec.lrow[ldof].hi; rdiag = T.rec.lrow[ldof].invw;
+          } else {
+            lo = T.d_lo[ldof]; hi = T.d_hi[ldof]; rdiag = T.d_invw[ldof];
+          }
+          rpos = (v & 1) ? (hi - q) : (q - lo);
           rmargin = 0;
-          rdiag = T.d_invw[ldof];
         } else {
           int ci = (info >> 3) & 0x3F, e = info & 7;
           int g1 = S.c_g1[ci], g2 = S.c_g2[ci];
-          int b1 = T.g_body[g1], b2 = T.g_body[g2];
-          int cd1 = T.g_condim[g1], cd2 = T.g_condim[g2];
+          int cd1, cd2;
+          float mu1, mu2, iw1, iw2, mg1, mg2;
+          if constexpr (PF) {
+            // the contact-row records of the two geoms, requested as soon as the geom ids are known: the body's
+            // inverse weight and dof chain are folded in, so nothing waits for g_body first
+            const rec_u4 ra0 = REC4(T, crow, g1, 0), ra1 = REC4(T, crow, g1, 1), rb0 = REC4(T, crow, g2, 0), rb1 = REC4(T, crow, g2, 1);
+            cd1 = (int)ra0.x; cd2 = (int)rb0.x;
+            mu1 = RECF(ra0.y); mu2 = RECF(rb0.y); mg1 = RECF(ra0.z); mg2 = RECF(rb0.z);
+            iw1 = RECF(ra0.w); iw2 = RECF(rb0.w);
+            cm1 = (unsigned long long)ra1.x | ((unsigned long long)ra1.y << 32);
+            cm2 = (unsigned long long)rb1.x | ((unsigned long long)rb1.y << 32);
+          } else {
+            const int b1 = T.g_body[g1], b2 = T.g_body[g2];
+            cd1 = T.g_condim[g1]; cd2 = T.g_condim[g2];
+            mu1 = T.g_mu[g1]; mu2 = T.g_mu[g2]; mg1 = T.g_margin[g1]; mg2 = T.g_margin[g2];
+            iw1 = T.b_invw[b1]; iw2 = T.b_invw[b2];
+            cm1 = T.b_chain[b1]; cm2 = T.b_chain[b2];
+          }
           int dim = cd1 > cd2 ? cd1 : cd2;
-          mu = fmaxf(T.g_mu[g1], T.g_mu[g2]);
+          mu = fmaxf(mu1, mu2);
           float fr[9];
           for (int i = 0; i < 9; i++) fr[i] = S.c_frame[ci][i];
-          float tran = T.b_invw[b1] + T.b_invw[b2];
+          float tran = iw1 + iw2;
           if (dim < 3) {
             rtype = 1;
             wl[0] = fr[0]; wl[1] = fr[1]; wl[2] = fr[2];
@@ -1220,9 +1265,8 @@ __device__ __forceinline__ void build_row(GDev &T, EnvLds &S, const int r, const
           }
           float off[3] = {S.c_pos[ci][0] - com[0], S.c_pos[ci][1] - com[1], S.c_pos[ci][2] - com[2]};
           cross3(wa, off, wl);
-          cm1 = T.b_chain[b1]; cm2 = T.b_chain[b2];
           rpos = S.c_dist[ci];
-          rmargin = fmaxf(T.g_margin[g1], T.g_margin[g2]);
+          rmargin = fmaxf(mg1, mg2);
         }
       }
       float vel = 0, jqs = 0;
