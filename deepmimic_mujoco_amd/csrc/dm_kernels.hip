@@ -137,9 +137,47 @@ __device__ __forceinline__ void factor_columns(float (&C)[DMK_NV]) {
 }
 // Triangular solves with the published sparse factor (lane = dof, rows UNSCALED: L[i][j] = M[i][j] * dinv[i]).
 // The broadcast value comes from a static lane, the factor entry from a per-lane base plus a static offset, and the
-// set of lanes a step touches is a compile-time lane mask: 5 instructions per step.
-// x <- L^-T x (then scaled by the caller).  negdep = -(depth of this lane's dof).
+// set of lanes a step touches is a compile-time lane mask.  The loops are
+//   solve_LT: for i = 33 .. 1:  x -= sel<anc(i)>(M(i, lane)) * (x dv)[i]
+//   solve_L:  for j = 0 .. 32:  x -= sel<desc(j)>(M(lane, j)) * (x dv)[j]
+// and a lane is updated along one tree path only, so they can be emitted in the order of topo::SOLVE_LT_SCHED / SOLVE_L_SCHED
+// (gen_topology.solve_schedule): the dofs of one depth (solve_L), or the five limbs (solve_LT), side by side, one scale and
+// one batch of broadcasts in front of their FMAs, the factor entries requested ahead of their round.  Every step stays a
+// wave-wide FMA whose multiplier is 0 outside its mask (no EXEC masking): a lane outside then sees the same set of
+// `x + (-+0)` operations as in the loop, each once, which keeps the sign of an exact zero and the spread of a NaN / Inf
+// broadcast over all lanes as they were; those steps commute with all others.  (That is why the table of solve_LT carries
+// the limb dofs' updates into the trunk lanes on a copy xt of the incoming x: on x itself a trunk lane would see a limb
+// dof's zero step besides its update.)
+template <bool LT>
+__device__ __forceinline__ float solve_sched(float x, const float dv, const int base, const float *M) {
+  constexpr const topo::SolveOp *tab = LT ? topo::SOLVE_LT_SCHED : topo::SOLVE_L_SCHED;
+  float s[topo::FS_SLOTS], ld[topo::SS_LSLOTS], xs = 0.f, xt = x;
+  StaticFor<0, (LT ? topo::SS_LT_NOPS : topo::SS_L_NOPS)>::run([&](auto nc) {
+    constexpr topo::SolveOp o = tab[decltype(nc)::value];
+    if constexpr (o.op == topo::SS_LOAD) ld[o.lslot] = LT ? M[topo::MADR[o.k] + topo::NANC[o.k] + base] : M[base - o.k];
+    if constexpr (o.op == topo::SS_SCALE) xs = x * dv;
+    if constexpr (o.op == topo::SS_BCAST) s[o.slot] = rl(xs, o.k);
+    if constexpr (o.op == topo::SS_FENCE) sgpr_batch<o.slot>(s);
+    if constexpr (o.op == topo::SS_FMA) {
+      constexpr unsigned long long mask = topo::solve_mask(o.kind, o.k);
+      static_assert((mask == 0) == (o.lslot == topo::SS_NOLOAD), "an entry is loaded for every non-empty mask");
+      float l = 0.f;
+      if constexpr (mask != 0) l = lane_sel<mask>(ld[o.lslot], 0.f);
+      if constexpr (o.kind == topo::SM_TRUNK) xt = fmaf(-l, s[o.slot], xt);
+      else x = fmaf(-l, s[o.slot], x);
+    }
+    if constexpr (o.op == topo::SS_MERGE) x = lane_sel<topo::TRUNK_MASK>(xt, x);
+    return true;
+  });
+  return x;
+}
+// x <- L^-T x (then scaled by the caller).  negdep = -(depth of this lane's dof).  The table order is built and tested but
+// switched off: with it the three-wave kernels spill 93 / 96 VGPRs against the limits 88 / 86.
+#ifndef DMK_SOLVE_LT_SCHED
+#define DMK_SOLVE_LT_SCHED 0
+#endif
 __device__ __forceinline__ float solve_LT(float x, const float dv, const int negdep, const float *M) {
+  if constexpr (DMK_SOLVE_LT_SCHED) return solve_sched<true>(x, dv, negdep, M);
   StaticFor<0, DMK_NV - 1>::run([&](auto ic) {
     constexpr int i = DMK_NV - 1 - decltype(ic)::value;   // 33 .. 1
     const float xi = rl(x * dv, i);
@@ -151,14 +189,7 @@ __device__ __forceinline__ float solve_LT(float x, const float dv, const int neg
 }
 // z <- z - M[:, j] x_j with x = z * dinv (D^-1 and L^-1 fused); mrow = MADR[lane] + depth(lane).
 __device__ __forceinline__ float solve_L(float x, const float dv, const int mrow, const float *M) {
-  StaticFor<0, DMK_NV - 1>::run([&](auto jc) {
-    constexpr int j = decltype(jc)::value;                 // 0 .. 32
-    const float xj = rl(x * dv, j);
-    const float l = lane_sel<topo::desc_mask(j)>(M[mrow - topo::NANC[j]], 0.f);
-    x = fmaf(-l, xj, x);
-    return true;
-  });
-  return x;
+  return solve_sched<false>(x, dv, mrow, M);
 }
 // Row I of the factor without its diagonal (the NANC[I] ancestor entries, nearest ancestor first) and dinv[I], read
 // through a pointer to the 16-byte aligned EnvLds with the widest loads the entries' alignment allows.

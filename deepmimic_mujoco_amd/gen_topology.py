@@ -31,22 +31,7 @@ def factor_schedule(parent, slots=FS_SLOTS):
     states between a VALU write of an SGPR and its VALU read; the update that feeds the next pivot leads its batch.
     """
     nv = len(parent)
-    kids = [[c for c in range(nv) if parent[c] == k] for k in range(nv)]
-    anc = []
-    for k in range(nv):
-        a, l = parent[k], []
-        while a >= 0:
-            l.append(a)
-            a = parent[a]
-        anc.append(l)                                       # nearest first
-    trunk = [k for k in range(nv) if any(len(kids[j]) > 1 for j in range(nv) if j == k or k in anc[j])]
-    limbs = []                                              # each from its leaf down to its first dof
-    for k in reversed(range(nv)):
-        if k not in trunk and not kids[k]:
-            limb = [k]
-            while parent[limb[-1]] not in trunk and parent[limb[-1]] >= 0:
-                limb.append(parent[limb[-1]])
-            limbs.append(limb)
+    anc, trunk, limbs = _tree(parent)
     ops = []
 
     def heads(ks, stages):
@@ -139,6 +124,191 @@ def check_factor_schedule(parent, ops):
     return True
 
 
+# Emission order of the triangular solves (solve_LT / solve_L): a list of (op, k, slot, lslot, kind).
+#   SS_LOAD  ld[lslot] = the lane's factor entry of row k (solve_LT) / of depth k (solve_L: one entry serves a whole level)
+#   SS_SCALE xs = x * dv          SS_BCAST s[slot] = readlane(xs, k)          SS_FENCE s[0..slot) are formed here
+#   SS_FMA   r = fma(-sel<mask(kind, k)>(ld[lslot], 0), s[slot], r), r = xt for SM_TRUNK and x otherwise; lslot SS_NOLOAD: the
+#            mask is empty and the multiplier is the constant 0
+#   SS_MERGE x = sel<trunk lanes>(xt, x)
+SS_LOAD, SS_SCALE, SS_BCAST, SS_FENCE, SS_FMA, SS_MERGE = range(6)
+# lanes of an FMA from dof k: its descendants (solve_L); its ancestors outside the trunk, inside it, all of them (solve_LT)
+SM_DESC, SM_LIMB, SM_TRUNK, SM_ANC = range(4)
+SS_NOLOAD = 255
+SS_AHEAD = 2        # serial rounds (one level, one trunk dof): entries are requested in pairs, this many rounds ahead
+SS_BATCH_AHEAD = 1  # limb rounds and trunk batches (up to FS_SLOTS entries each): requested this many rounds ahead
+
+
+def _tree(parent):
+    """anc (nearest first), trunk (dofs with a branching dof in their subtree), limbs (each from its leaf down), highest first."""
+    nv = len(parent)
+    kids = [[c for c in range(nv) if parent[c] == k] for k in range(nv)]
+    anc = []
+    for k in range(nv):
+        a, l = parent[k], []
+        while a >= 0:
+            l.append(a)
+            a = parent[a]
+        anc.append(l)
+    trunk = [k for k in range(nv) if any(len(kids[j]) > 1 for j in range(nv) if j == k or k in anc[j])]
+    limbs = []
+    for k in reversed(range(nv)):
+        if k not in trunk and not kids[k]:
+            limb = [k]
+            while parent[limb[-1]] not in trunk and parent[limb[-1]] >= 0:
+                limb.append(parent[limb[-1]])
+            limbs.append(limb)
+    return anc, trunk, limbs
+
+
+def solve_mask(parent, kind, k):
+    """The lanes (dofs) an SS_FMA of this kind from dof k updates."""
+    anc, trunk, _ = _tree(parent)
+    if kind == SM_DESC:
+        return [i for i in range(len(parent)) if k in anc[i]]
+    return [j for j in anc[k] if kind == SM_ANC or (j in trunk) == (kind == SM_TRUNK)]
+
+
+def _emit_rounds(rounds, slots):
+    """rounds: [(request_at, [load keys], body)] with body a list of (op, k, slot, load key or None, kind) -> ops.  The loads of
+    a round are emitted at the head of round `request_at`; a load slot is free again after the last FMA that reads it."""
+    ops, held, free, top = [], {}, [], 0
+    for r, (_, _, body) in enumerate(rounds):
+        for at, keys, _ in rounds:
+            if at == r:
+                for key in keys:
+                    if free:
+                        held[key] = free.pop(0)
+                    else:
+                        held[key], top = top, top + 1
+                    ops.append((SS_LOAD, key[1], 0, held[key], 0))
+        last = {key: n for n, (op, k, s, key, kind) in enumerate(body) if key is not None}
+        for n, (op, k, s, key, kind) in enumerate(body):
+            ops.append((op, k, s, SS_NOLOAD if key is None else held[key], kind))
+            if key is not None and last[key] == n:
+                free.append(held.pop(key))
+                free.sort()
+    assert not held and all(0 <= o[2] <= slots for o in ops)
+    return ops
+
+
+def _serial_request(first, r):
+    """Serial rounds first, first+1, ...: the entries of rounds 2m, 2m+1 go out together, SS_AHEAD rounds before round 2m (the
+    first ones at the head of the round before the serial part, if there is one)."""
+    return max(first - 1, 0, first + 2 * ((r - first) // 2) - SS_AHEAD)
+
+
+def solve_schedule(parent, slots=FS_SLOTS):
+    """-> (ops of solve_L, ops of solve_LT): orders that keep every bit of the serial loops.
+
+    Both loops are `for k: s = (x * dv)[k]; x[lanes(k)] -= M[..] * s`, each step a wave-wide FMA whose multiplier is 0 outside
+    lanes(k).  A lane's value is fixed by the sequence of the FMAs that update it and by the x_k each of them reads; the FMAs
+    with multiplier 0 only add a signed zero (or spread a NaN), they commute with every other step, and each lane must see each
+    of them exactly once.  solve_L (k ascending, lanes = descendants of k): a lane is updated by its ancestors only, which lie on
+    one path, so the dofs of one depth go together: one scale, their broadcasts as a batch, their FMAs; the factor entry
+    M[lane][ancestor at depth d] is the same load for the whole level.  solve_LT (k descending, lanes = ancestors of k): (a) the
+    limbs side by side from their leaves down, each FMA on the limb's own lanes; (b) the limb dofs' updates into the trunk in
+    descending k, on a copy xt of the incoming x (so that a trunk lane sees one step per limb dof, as in the loop, and not the
+    zero step of (a) besides), the scalars broadcast again from the finished limb lanes in batches of `slots`; x takes the trunk
+    lanes of xt; (c) the trunk dofs serially.  Factor entries are requested ahead of the round that uses them: a limb round or a
+    batch one round ahead, serial rounds in pairs SS_AHEAD rounds ahead.  (The kernels walk the solve_L table; the solve_LT
+    table is compiled in only with -DDMK_SOLVE_LT_SCHED=1, see csrc/dm_kernels.hip.)
+    """
+    nv = len(parent)
+    anc, trunk, limbs = _tree(parent)
+    depth = [len(a) for a in anc]
+    desc = [[i for i in range(nv) if k in anc[i]] for k in range(nv)]
+
+    def round_of(ks, kind, masks, key_of, scale=True):
+        body = [(SS_SCALE, 0, 0, None, 0)] if scale else []
+        body += [(SS_BCAST, k, s, None, 0) for s, k in enumerate(ks)] + [(SS_FENCE, 0, len(ks), None, 0)]
+        body += [(SS_FMA, k, s, key_of(k) if masks[k] else None, kind) for s, k in enumerate(ks)]
+        return sorted({key_of(k) for k in ks if masks[k]}), body
+
+    # solve_L: dofs 0 .. nv-2 by depth
+    levels = [[j for j in range(nv - 1) if depth[j] == d] for d in range(max(depth) + 1)]
+    levels = [l for l in levels if l]
+    assert all(len(l) <= slots for l in levels)
+    rounds = []
+    for r, ks in enumerate(levels):
+        keys, body = round_of(ks, SM_DESC, desc, lambda k: ("d", depth[k]))
+        rounds.append((_serial_request(0, r), keys, body))
+    ops_l = _emit_rounds(rounds, slots)
+
+    # solve_LT: dofs nv-1 .. 1
+    rounds = []
+    nlimb = max((len(l) for l in limbs), default=0)
+    own = {k: [j for j in anc[k] if j not in trunk] for k in range(nv)}
+    tr = {k: [j for j in anc[k] if j in trunk] for k in range(nv)}
+    for r in range(nlimb):                                                      # (a)
+        keys, body = round_of([l[r] for l in limbs if len(l) > r], SM_LIMB, own, lambda k: ("a", k))
+        rounds.append((max(0, r - SS_BATCH_AHEAD), keys, body))
+    later = sorted((k for l in limbs for k in l), reverse=True)
+    for b in range(0, len(later), slots):                                       # (b)
+        keys, body = round_of(later[b:b + slots], SM_TRUNK, tr, lambda k: ("b", k), scale=(b == 0))
+        rounds.append((len(rounds) - SS_BATCH_AHEAD, keys, body))
+    rounds[-1][2].append((SS_MERGE, 0, 0, None, 0))
+    first_c = len(rounds)
+    for k in sorted(trunk, reverse=True):                                       # (c)
+        if k >= 1:
+            keys, body = round_of([k], SM_ANC, anc, lambda k: ("c", k))
+            rounds.append((_serial_request(first_c, len(rounds)), keys, body))
+    ops_lt = _emit_rounds(rounds, slots)
+    check_solve_schedule(parent, ops_l, ops_lt)
+    return ops_l, ops_lt
+
+
+def check_solve_schedule(parent, ops_l, ops_lt):
+    """The rules of solve_schedule(), by symbolic execution of the op lists; raises AssertionError with the offending op.
+
+    Every lane carries the list of the dofs whose FMA has updated it and the set of the dofs whose zero step it has seen.  A
+    broadcast of dof k must read a lane whose list is the serial loop's complete one; at the end every dof lane holds that list
+    and has seen every other broadcast dof's zero step exactly once; every FMA reads a fenced scalar of its own dof and a factor
+    entry loaded for it that no other load has overwritten."""
+    nv = len(parent)
+    anc, trunk, _ = _tree(parent)
+    depth = [len(a) for a in anc]
+    for lt, ops in ((False, ops_l), (True, ops_lt)):
+        srcs = list(range(nv - 1, 0, -1)) if lt else list(range(nv - 1))
+        want = {i: [k for k in srcs if (i in anc[k] if lt else k in anc[i])] for i in range(nv)}
+        real = {"x": {i: [] for i in range(nv)}, "xt": {i: [] for i in range(nv)}}
+        zero = {"x": {i: [] for i in range(nv)}, "xt": {i: [] for i in range(nv)}}
+        xs, s, ld = None, {}, {}
+        for n, (op, k, slot, lslot, kind) in enumerate(ops):
+            if op == SS_LOAD:
+                ld[lslot] = k
+            elif op == SS_SCALE:
+                xs = {i: list(real["x"][i]) for i in range(nv)}
+            elif op == SS_BCAST:
+                assert xs is not None and xs[k] == want[k], "op %d: broadcast of dof %d before the last update into its lane" % (n, k)
+                s[slot] = (k, False)
+            elif op == SS_FENCE:
+                for t in range(slot):
+                    s[t] = (s[t][0], True)
+            elif op == SS_FMA:
+                assert s.get(slot) == (k, True), "op %d: FMA of dof %d reads slot %d, which does not hold its fenced scalar" % (n, k, slot)
+                assert kind == SM_DESC if not lt else kind in (SM_LIMB, SM_TRUNK, SM_ANC), "op %d: mask kind %d" % (n, kind)
+                lanes = solve_mask(parent, kind, k)
+                if lanes:
+                    assert ld.get(lslot) == (k if lt else depth[k]), "op %d: FMA of dof %d reads load slot %d, which does not hold its entry" % (n, k, lslot)
+                else:
+                    assert lslot == SS_NOLOAD, "op %d: an entry for an empty mask" % n
+                reg = "xt" if kind == SM_TRUNK else "x"
+                for i in range(nv):
+                    (real if i in lanes else zero)[reg][i].append(k)
+                    if i in lanes:
+                        assert real[reg][i] == want[i][:len(real[reg][i])], "op %d: update of dof %d into lane %d out of order" % (n, k, i)
+            elif op == SS_MERGE:
+                for i in trunk:
+                    assert not real["x"][i], "op %d: x's trunk lane %d was updated before the merge" % (n, i)
+                    real["x"][i], zero["x"][i] = real["xt"][i], zero["xt"][i]
+            else:
+                raise AssertionError("op %d: unknown op %d" % (n, op))
+        for i in range(nv):
+            assert real["x"][i] == want[i], "lane %d ends with the updates %s" % (i, real["x"][i])
+            assert sorted(real["x"][i] + zero["x"][i]) == sorted(srcs), "lane %d does not see every step once" % i
+    return True
+
+
 def render(model):
     parent = [int(x) for x in model.dof_parent]
     nanc = []
@@ -197,8 +367,30 @@ def render(model):
     names = ("FS_DIAG", "FS_RCP", "FS_SCALE", "FS_BCAST", "FS_FMA", "FS_FENCE", "FS_DFENCE")
     for b in range(0, len(sched), 6):
         lines.append("  " + " ".join("{%s, %d, %d, %d}," % (names[op], k, i, s) for op, k, i, s in sched[b:b + 6]))
+    lines.append("};")
+    ops_l, ops_lt = solve_schedule(parent)
+    _, trunk, _ = _tree(parent)
     lines += [
-        "};",
+        "// Emission order of the triangular solves solve_L (by depth level) and solve_LT (limbs side by side, their updates into the",
+        "// trunk on the copy xt, the trunk serially), factor entries requested ahead of their round (gen_topology.solve_schedule).",
+        "enum { SS_LOAD, SS_SCALE, SS_BCAST, SS_FENCE, SS_FMA, SS_MERGE };",
+        "enum { SM_DESC, SM_LIMB, SM_TRUNK, SM_ANC };",
+        "struct SolveOp { unsigned char op, k, slot, lslot, kind; };",
+        "constexpr int SS_NOLOAD = %d;" % SS_NOLOAD,
+        "constexpr int SS_LSLOTS = %d;" % (1 + max(o[3] for o in ops_l + ops_lt if o[3] != SS_NOLOAD)),
+        "constexpr unsigned long long TRUNK_MASK = 0x%xull;" % sum(1 << k for k in trunk),
+        "constexpr unsigned long long solve_mask(int kind, int k) {",
+        "  return kind == SM_DESC ? desc_mask(k) : kind == SM_LIMB ? anc_mask(k) & ~TRUNK_MASK : kind == SM_TRUNK ? anc_mask(k) & TRUNK_MASK : anc_mask(k);",
+        "}",
+    ]
+    snames = ("SS_LOAD", "SS_SCALE", "SS_BCAST", "SS_FENCE", "SS_FMA", "SS_MERGE")
+    knames = ("SM_DESC", "SM_LIMB", "SM_TRUNK", "SM_ANC")
+    for tag, ops in (("L", ops_l), ("LT", ops_lt)):
+        lines += ["constexpr int SS_%s_NOPS = %d;" % (tag, len(ops)), "constexpr SolveOp SOLVE_%s_SCHED[SS_%s_NOPS] = {" % (tag, tag)]
+        for b in range(0, len(ops), 5):
+            lines.append("  " + " ".join("{%s, %d, %d, %d, %s}," % (snames[op], k, s, ls, knames[kind]) for op, k, s, ls, kind in ops[b:b + 5]))
+        lines.append("};")
+    lines += [
         "}  // namespace topo",
         "",
     ]
