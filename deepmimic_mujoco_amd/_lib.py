@@ -275,6 +275,11 @@ class EngineBase:
     def step_forced(self, qpos, qvel, out):
         self._call("step_forced", qpos, qvel, out["obs"], out["rew"], out["done"], out.get("terms"), out.get("reason"))
 
+    def step_active(self, actions, env_ids, nslots, out):
+        """``dm_step_active`` / ``dmg1_step_active``: the envs listed in ``env_ids[:nslots]`` (int32 device tensor, entries < 0
+        skipped) take one step without auto-reset; ``actions`` and the rows of ``out`` stay indexed by env."""
+        self._call("step_active", actions, env_ids, int(nslots), out["obs"], out["rew"], out["done"], out.get("terms"), out.get("reason"))
+
     def get_counters(self):
         """(idx_curr int32[N], episode_length int32[N], episode_reward float32[N])"""
         t = self.torch
@@ -335,11 +340,6 @@ class HipEngine(EngineBase):
         t = None if clip_ids is None else clip_ids.to(self.device, self.torch.int32).contiguous()
         self._call("set_env_clips", t)
         self._keep = t
-
-    def step_active(self, actions, env_ids, nslots, out):
-        """``dm_step_active``: the envs listed in ``env_ids[:nslots]`` (int32 device tensor, entries < 0 skipped) take one step without
-        auto-reset; ``actions`` and the rows of ``out`` stay indexed by env."""
-        self._call("step_active", actions, env_ids, int(nslots), out["obs"], out["rew"], out["done"], out.get("terms"), out.get("reason"))
 
     # ---- state
     def physics_step(self, actions):

@@ -134,10 +134,13 @@ struct Launch {
   float *jt, *bt, *ar;       // per-env scratch: J^T [44][MAXROW], (D^-1/2 L^-T J^T) [44][MAXROW], A [MAXROW][MAXROW]
   float *rows;               // per-env scratch: R, aref -> b, force, friction-loss bound, meta (type | id << 2): [5][MAXROW]
   float *sepc;               // per-env separating-direction cache of the MPR pairs: [SEPC + 1][4]
-  const int32_t *order;      // STEP: workgroup -> env, heaviest envs first (g1_schedule_kernel), or null
+  const int32_t *order;      // STEP: workgroup -> env: heaviest envs first (g1_schedule_kernel), the slot list of dmg1_step_active
+                             // (an entry outside [0, N) ends its workgroup at once), or null
   int32_t *cost;             // STEP: per-env work estimate of this step, or null
   ClipDev clips[DMG1_MAX_CLIPS];   // DPEnv: the env's clip id picks one (multi-clip batches); DPCombinedEnv: 0..2 = walk, run, getup
-  int32_t task, amnesty_steps, to_getup_len, pad2;
+  int32_t task, amnesty_steps, to_getup_len;
+  int32_t nslots;            // workgroups of this launch that have an env (N, or the slots of dmg1_step_active); N stays the engine's
+                             // env count: every per-env layout (state rows, queue blocks, ticket lists) is built on it
   int32_t N, mode, auto_reset, max_ep_length, run_forward, pad;
   float vel_obs_scale, high_z, obs_bound;
   uint64_t seed;
@@ -2501,8 +2504,9 @@ __device__ __forceinline__ void step_write_back(const Launch &P, const int env, 
 // The monolithic kernel: one wave runs the whole step (or the single evaluation of the other modes) of its env.
 extern "C" __global__ void __launch_bounds__(64, 2) g1_step_kernel(Launch P) {
   const int lane = threadIdx.x;
-  if ((int)blockIdx.x >= P.N) return;
+  if ((int)blockIdx.x >= P.nslots) return;
   const int env = (P.order && P.mode == MODE_STEP) ? P.order[blockIdx.x] : (int)blockIdx.x;
+  if ((unsigned)env >= (unsigned)P.N) return;   // a slot without an env (-1 of a padded list): nothing is read or written
   const Dev &T = *P.T;
   const int mode = P.mode;
 #ifdef G1_PROFILE
@@ -2659,8 +2663,9 @@ __device__ __forceinline__ int gather_contacts(const Dev &T, const Launch &P, co
 
 extern "C" __global__ void __launch_bounds__(64, 2) g1_env_kernel(Launch P) {
   const int lane = threadIdx.x;
-  if ((int)blockIdx.x >= P.N) return;
+  if ((int)blockIdx.x >= P.nslots) return;
   const int env = P.order ? P.order[blockIdx.x] : (int)blockIdx.x;
+  if ((unsigned)env >= (unsigned)P.N) return;   // a slot without an env, in every round: not even its working-set slot is touched
   const Dev &T = *P.T;
   char *ws = P.ws + (size_t)env * WS_BYTES;
   int *wctx = reinterpret_cast<int *>(ws + WS_CTX_OFF);
@@ -2773,6 +2778,34 @@ extern "C" __global__ void __launch_bounds__(1024) g1_schedule_kernel(const int3
   for (int i = t; i < N; i += 1024) order[atomicAdd(&base[63 - min(63, (int)((float)cost[i] * sc))], 1)] = i;
 }
 
+// The same over the slot list of dmg1_step_active: the listed envs by their costs, heaviest first, into the engine's own order
+// (the caller's list is only read); slots without an env (an entry outside [0, N)) go last, as -1.  nslots <= N entries are written.
+extern "C" __global__ void __launch_bounds__(1024) g1_schedule_list_kernel(const int32_t *cost, const int32_t *list, int nslots, int N,
+                                                                             int32_t *order) {
+  __shared__ int hist[65], base[65], cmax;
+  const int t = threadIdx.x;
+  if (t < 65) hist[t] = 0;
+  if (t == 0) cmax = 1;
+  __syncthreads();
+  int m = 1;
+  for (int i = t; i < nslots; i += 1024) { const int e = list[i]; if ((unsigned)e < (unsigned)N) m = max(m, cost[e]); }
+  atomicMax(&cmax, m);
+  __syncthreads();
+  const float sc = 64.f / ((float)cmax + 1.f);
+  for (int i = t; i < nslots; i += 1024) {
+    const int e = list[i];
+    atomicAdd(&hist[(unsigned)e < (unsigned)N ? 63 - min(63, max(0, (int)((float)cost[e] * sc))) : 64], 1);
+  }
+  __syncthreads();
+  if (t == 0) { int a = 0; for (int b = 0; b < 65; b++) { base[b] = a; a += hist[b]; } }
+  __syncthreads();
+  for (int i = t; i < nslots; i += 1024) {
+    const int e = list[i];
+    const bool on = (unsigned)e < (unsigned)N;
+    order[atomicAdd(&base[on ? 63 - min(63, max(0, (int)((float)cost[e] * sc))) : 64], 1)] = on ? e : -1;
+  }
+}
+
 extern "C" __global__ void g1_gather_kernel(const float *state, int N, int off, int n, int stride, float *out) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= N * n) return;
@@ -2800,6 +2833,7 @@ struct DmG1Engine {
   int L[DMG1_MAX_CLIPS] = {}, flags[DMG1_MAX_CLIPS] = {};
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   bool timed = false;
+  bool active_lpt = true;   // dmg1_step_active orders its slot list longest-first (from 512 envs up, as dmg1_step)
   // split pipeline (dmg1_step of batches >= 512 envs, or DmG1Config.pipeline = 2)
   bool split = false;
   char *dWs = nullptr;
@@ -3157,11 +3191,14 @@ extern "C" int dmg1_load_clip(DmG1Handle e, int clip_id, int L, const double *q,
   return DM_OK;
 }
 
-static int g1_launch(DmG1Engine *e, g1::Launch &P, void *stream, bool time_it) {
+// slots / nslots: the slot list of dmg1_step_active (MODE_STEP only); null = all N envs.  The pipeline (e->split) and every layout
+// constant come from the engine's N; nslots sizes the grids only.
+static int g1_launch(DmG1Engine *e, g1::Launch &P, void *stream, bool time_it, const int32_t *slots = nullptr, int nslots = 0) {
   P.T = e->dT; P.mesh_vert = e->dMesh; P.mesh_oidx = e->dOidx; P.mesh_clus = e->dClus; P.state = e->dState; P.jt = e->dJT; P.bt = e->dBT; P.ar = e->dAR; P.rows = e->dRowsE; P.sepc = e->dSepc;
   for (int c = 0; c < DMG1_MAX_CLIPS; c++) { P.clips[c].rows = e->dRows[c]; P.clips[c].reset = e->dReset[c]; P.clips[c].com = e->dCom[c]; P.clips[c].L = e->L[c]; P.clips[c].flags = e->flags[c]; }
   P.task = e->cfg.task; P.amnesty_steps = e->cfg.amnesty_steps; P.to_getup_len = e->cfg.to_getup_len;
-  P.N = e->N; P.auto_reset = e->cfg.auto_reset; P.max_ep_length = e->cfg.max_ep_length;
+  const int nl = slots ? nslots : e->N;
+  P.N = e->N; P.nslots = nl; P.auto_reset = slots ? 0 : e->cfg.auto_reset; P.max_ep_length = e->cfg.max_ep_length;
   P.vel_obs_scale = e->cfg.vel_obs_scale; P.high_z = e->cfg.high_z; P.obs_bound = e->cfg.obs_bound; P.seed = e->cfg.seed;
   P.debug = e->dDebug;
   if (!e->L[0]) return g1_fail(e, DM_EINVAL, "no clip loaded (dmg1_load_clip clip 0 first)");
@@ -3174,9 +3211,11 @@ static int g1_launch(DmG1Engine *e, g1::Launch &P, void *stream, bool time_it) {
 #endif
   hipStream_t s = (hipStream_t)stream;
   if (time_it) hipEventRecord(e->ev0, s);
+  if (slots) P.order = slots;
   if (P.mode == g1::MODE_STEP && e->N >= 512 && lpt) {   // longest-first order from the previous step's costs
-    hipLaunchKernelGGL(g1::g1_schedule_kernel, dim3(1), dim3(1024), 0, s, e->dCost, e->dOrder, e->N);
-    P.order = e->dOrder;
+    if (!slots) hipLaunchKernelGGL(g1::g1_schedule_kernel, dim3(1), dim3(1024), 0, s, e->dCost, e->dOrder, e->N);
+    else if (e->active_lpt) hipLaunchKernelGGL(g1::g1_schedule_list_kernel, dim3(1), dim3(1024), 0, s, e->dCost, slots, nl, e->N, e->dOrder);
+    if (!slots || e->active_lpt) P.order = e->dOrder;
   }
   if (P.mode == g1::MODE_STEP) P.cost = e->dCost;
   if (P.mode == g1::MODE_STEP && e->split) {
@@ -3188,17 +3227,17 @@ static int g1_launch(DmG1Engine *e, g1::Launch &P, void *stream, bool time_it) {
     memset(&Q, 0, sizeof Q);
     Q.T = e->dT; Q.mesh_vert = e->dMesh; Q.mesh_oidx = e->dOidx; Q.mesh_clus = e->dClus; Q.pq_geo = e->dPqGeo; Q.pq_pair = e->dPqPair;
     Q.pq_cnt = e->dPqCnt; Q.pq_con = e->dPqCon; Q.tick = e->dTick; Q.sepc2 = e->dSepc2; Q.N = e->N;
-    const int pair_waves = std::min(e->N * 8, 256 * 4 * G1_PAIR_WAVES);   // persistent: every wave pulls tickets until the queue is empty
+    const int pair_waves = std::min(nl * 8, 256 * 4 * G1_PAIR_WAVES);   // persistent: every wave pulls tickets until the queue is empty
     for (int r = 0; r < 6; r++) {
       P.round = r;
-      hipLaunchKernelGGL(g1::g1_env_kernel, dim3(e->N), dim3(64), 0, s, P);
+      hipLaunchKernelGGL(g1::g1_env_kernel, dim3(nl), dim3(64), 0, s, P);
       if (r < 5) {
         Q.qctr = e->dQctr + 4 * r;
         hipLaunchKernelGGL(g1::g1_pair_kernel, dim3(pair_waves), dim3(64), 0, s, Q);
       }
     }
   } else {
-    hipLaunchKernelGGL(g1::g1_step_kernel, dim3(e->N), dim3(64), 0, s, P);
+    hipLaunchKernelGGL(g1::g1_step_kernel, dim3(nl), dim3(64), 0, s, P);
   }
   if (time_it) { hipEventRecord(e->ev1, s); e->timed = true; }
   return hipGetLastError() == hipSuccess ? DM_OK : g1_fail(e, DM_EHIP, "kernel launch failed");
@@ -3220,6 +3259,21 @@ extern "C" int dmg1_step(DmG1Handle e, const float *actions, float *obs, float *
   P.mode = g1::MODE_STEP; P.actions = actions; P.obs = obs; P.rew = rew; P.done = done; P.terms = terms; P.reason = reason;
   P.terminal_obs = terminal_obs;
   return g1_launch(e, P, stream, true);
+}
+extern "C" int dmg1_step_active(DmG1Handle e, const float *actions, const int32_t *env_ids, int nslots, float *obs, float *rew,
+                                uint8_t *done, float *terms, int32_t *reason, void *stream) {
+  if (!e) return DM_EINVAL;
+  if (!actions || !env_ids || !obs || !rew || !done || nslots < 1 || nslots > e->N) return g1_fail(e, DM_EINVAL, "dmg1_step_active: bad argument");
+  if (!e->L[0]) return g1_fail(e, DM_EINVAL, "no clip loaded");
+  g1::Launch P;
+  memset(&P, 0, sizeof P);
+  P.mode = g1::MODE_STEP; P.actions = actions; P.obs = obs; P.rew = rew; P.done = done; P.terms = terms; P.reason = reason;
+  return g1_launch(e, P, stream, true, env_ids, nslots);   // no auto-reset; the pipeline of the whole batch, however few envs are left
+}
+extern "C" int dmg1_set_active_schedule(DmG1Handle e, int on) {
+  if (!e) return DM_EINVAL;
+  e->active_lpt = on != 0;
+  return DM_OK;
 }
 extern "C" int dmg1_step_forced(DmG1Handle e, const float *qpos, const float *qvel, float *obs, float *rew, uint8_t *done,
                                 float *terms, int32_t *reason, void *stream) {

@@ -118,7 +118,8 @@ class EvalDashboardCallback:
     """`callback=` of `PPO.learn`: evaluate every `every_n_global_steps` (src/sb3_ppo.py:143-190; called once per PPO iteration).
 
     ``batch_env`` (an ``auto_reset=False`` batch env, default None = off): every evaluation point also runs the batched evaluation
-    (evaluation.evaluation_record: one deterministic episode per start frame of ``batch_start_frames``) and appends
+    (evaluation.evaluation_record: one deterministic episode per start frame of ``batch_start_frames``, finished envs leaving the
+    launches on either robot, ``compact="all"``) and appends
     ``global_step,episodes,ep_rew_mean,ep_rew_std,ep_len_mean,frac_reached_cap`` to ``eval_batch.csv`` next to ``log.csv``."""
 
     def __init__(self, eval_env, run_name, log_wandb=False, every_n_global_steps=1_000_000, out_root=None, figures=True, max_steps=None,

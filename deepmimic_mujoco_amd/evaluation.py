@@ -5,9 +5,13 @@ frame, src/play_g1_run_polar_breeze.py:30-49) do, for N episodes at once.
 One evaluation is N episodes, one per env of an ``auto_reset=False`` batch env.  Every episode starts from a chosen reference
 frame, acts with the deterministic policy and is stopped at its first ``done`` or at ``max_steps``.  The bookkeeping is one launch
 per env step (``dm_eval_advance``, csrc/dm_eval.hip): episode sums in fp64 on the device, finished envs retired, and the ascending
-list of the envs still alive rebuilt.  On the humanoid engine that list is the slot list of ``dm_step_active``: a finished env —
-a body lying on the floor, the most expensive kind of env there is — is not launched any more, and its state stays
-what its terminal step left ("frozen").  The host reads four bytes per engine every ``sync_every`` steps and nothing else.
+list of the envs still alive rebuilt.  That list is the slot list of ``dm_step_active`` (humanoid3d) and ``dmg1_step_active``
+(Unitree G1, both pipelines, both tasks): a finished env — a body lying on the floor, the most expensive kind of env there is
+ — is not launched any more, and its state stays what its terminal step left ("frozen").  ``compact`` picks the
+engines that take that route (``resolve_compact``): ``True`` the humanoid engines, ``"all"`` every engine that has
+``step_active``, the G1 included — what ``evaluation_record`` and with it ``train.py --eval-envs`` and
+``EvalDashboardCallback(batch_env=...)`` ask for.  Episode results are bit-identical on either route.  The host reads four bytes
+per engine every ``sync_every`` steps and nothing else.
 """
 from __future__ import annotations
 
@@ -88,14 +92,27 @@ def clip_length(env):
     return int(L[0] if isinstance(L, dict) else L)
 
 
+def resolve_compact(compact, humanoid):
+    """Whether ``BatchEvaluator(compact=...)`` launches only the live envs, on an env whose engines are all humanoid3d
+    (``humanoid`` true) or not (Unitree G1): ``True`` compacts the humanoid engines alone, ``"all"`` every engine that has
+    ``step_active``, ``False`` none.  Anything else is a ``ValueError``."""
+    if isinstance(compact, str) and compact == "all":
+        return True
+    if isinstance(compact, (bool, np.bool_)):
+        return bool(compact) and bool(humanoid)
+    raise ValueError("compact is True (humanoid3d engines only), \"all\" (every engine) or False, not %r" % (compact,))
+
+
 # ------------------------------------------------------------------------------------------ the evaluator
 class BatchEvaluator:
     """``run`` = one episode per env of ``env`` (any ``HipBatchEnv`` built with ``auto_reset=False``, any ``sub_batches``).
 
-    ``compact=True``: on engines that have ``step_active`` (humanoid3d) only the envs still alive are launched.  Everything
-    else — the Unitree G1 engines, ``compact=False`` — steps all envs with the plain ``step_tensor`` and only the bookkeeping
-    ignores the finished ones (their engine state moves on; nothing reads it).  ``sync_every``: env steps between two reads of
-    the live count; the results do not depend on it."""
+    ``compact`` (``resolve_compact``): ``True`` launches only the envs still alive on the humanoid3d engines
+    (``dm_step_active``), ``"all"`` on the Unitree G1 engines too (``dmg1_step_active``; with ``sub_batches > 1`` each engine on
+    its own stream, as the env's own step).  A finished env's engine state then stays what its terminal step left.  Everything
+    else — ``compact=False``, a G1 env under ``True`` — steps all envs with the plain ``step_tensor`` and only the bookkeeping
+    ignores the finished ones (their engine state moves on; nothing reads it).  The episodes are the same bit for bit.
+    ``sync_every``: env steps between two reads of the live count; the results do not depend on it."""
 
     def __init__(self, env, compact=True, sync_every=16):
         if getattr(env, "auto_reset", True):
@@ -108,7 +125,9 @@ class BatchEvaluator:
         self.sync_every = int(sync_every)
         from ._lib import HipEngine
         self.humanoid = all(isinstance(e, HipEngine) for e in env.engines)
-        self.compact = bool(compact) and self.humanoid
+        self.compact = resolve_compact(compact, self.humanoid)
+        if self.compact and not all(hasattr(e, "step_active") for e in env.engines):
+            raise ValueError("compact=%r: an engine of this env has no step_active" % (compact,))
         self.N, self.device = int(env.num_envs), env.device
         self.obs_dim, self.terms_dim = int(env.out["obs"].shape[1]), int(env.out["terms"].shape[1])
         self.launched_env_steps = 0        # env steps handed to the step kernels by the last run (an upper bound under compaction)
@@ -145,6 +164,26 @@ class BatchEvaluator:
                       out["reason"][sl], out["terms"][sl], out["obs"][sl], self.obs_dim, self.alive[sl], self.ep_len[sl],
                       self.ep_ret[sl], self.ep_terms[sl], self.ep_reason[sl], self.last_obs[sl], self.env_ids[sl],
                       self.counts[k:k + 1], dev_index, device=self.device)
+
+    def _step_active(self, actions, nslots):
+        """One step of the live envs of every engine.  A G1 env of several engines forks each engine's launches onto that
+        engine's stream and joins them back, as ``HipG1VecEnv._step_engines`` does for the plain step."""
+        t, env = self.torch, self.env
+        work = [x for x in zip(env.engines, env.sub_out, env.sub_slices, nslots) if x[3] > 0]
+        if self.humanoid or len(env.engines) == 1:
+            for e, o, sl, ns in work:
+                e.step_active(actions[sl], self.env_ids[sl], ns, o)
+            return
+        cur = t.cuda.current_stream(self.device)
+        if getattr(env, "_streams", None) is None:
+            from .streams import concurrent_streams
+            env._streams = concurrent_streams(self.device, len(env.engines))
+        fork = cur.record_event()
+        for (e, o, sl, ns), s in zip(work, [env._streams[k] for k, ns in enumerate(nslots) if ns > 0]):
+            s.wait_event(fork)
+            with t.cuda.stream(s):
+                e.step_active(actions[sl], self.env_ids[sl], ns, o)
+            cur.wait_event(s.record_event())
 
     def run(self, act_fn, start_frames=None, max_steps=None):
         """``act_fn(obs [N, D]) -> actions [N, A]`` on device tensors (all N rows, every step; rows of finished envs are ignored).
@@ -188,10 +227,7 @@ class BatchEvaluator:
         while steps < max_steps:
             actions = act_fn(obs)
             if self.compact:
-                actions = actions.contiguous()
-                for e, o, sl, ns in zip(env.engines, env.sub_out, env.sub_slices, nslots):
-                    if ns > 0:
-                        e.step_active(actions[sl], self.env_ids[sl], ns, o)
+                self._step_active(actions.contiguous(), nslots)
                 launched += sum(nslots)
             else:
                 env.step_tensor(actions)
@@ -302,22 +338,24 @@ def run_episodes(model, env, n_eval_episodes=None, start_frames="all", determini
 
 
 def evaluate_policy(model, env, n_eval_episodes=None, start_frames="all", deterministic=True, max_steps=None,
-                    return_episode_rewards=False):
+                    return_episode_rewards=False, compact=True):
     """``stable_baselines3.common.evaluation.evaluate_policy`` [EXT] on a batch env: ``(mean_reward, std_reward)``, or with
     ``return_episode_rewards`` the lists ``(episode_rewards, episode_lengths)`` in episode order.  When there are more episodes than
-    envs the evaluator runs ceil(episodes / num_envs) rounds.  See ``run_episodes`` for ``start_frames``."""
-    results = run_episodes(model, env, n_eval_episodes, start_frames, deterministic, max_steps)
+    envs the evaluator runs ceil(episodes / num_envs) rounds.  See ``run_episodes`` for ``start_frames``, ``BatchEvaluator``
+    for ``compact`` (``"all"`` also leaves finished Unitree G1 envs out of the launches; same numbers)."""
+    results = run_episodes(model, env, n_eval_episodes, start_frames, deterministic, max_steps, compact)
     if return_episode_rewards:
         return ([float(x) for r in results for x in _np(r.ep_ret)], [int(x) for r in results for x in _np(r.ep_len)])
     s = episode_statistics(results, max_ep_length(env))
     return s["ep_rew_mean"], s["ep_rew_std"]
 
 
-def evaluation_record(model, env, global_step, start_frames="all", n_eval_episodes=None, max_steps=None):
-    """The six fields of one evaluation point (``eval_batch.csv`` of ``EvalDashboardCallback``, ``"eval"`` of ``train.py --json``)."""
+def evaluation_record(model, env, global_step, start_frames="all", n_eval_episodes=None, max_steps=None, compact="all"):
+    """The six fields of one evaluation point (``eval_batch.csv`` of ``EvalDashboardCallback``, ``"eval"`` of ``train.py --json``).
+    ``compact="all"``: finished envs leave the launches on either robot (DESIGN §16 has the measurement behind the default)."""
     if is_combined(env) or (isinstance(start_frames, str) and is_multi_clip(env)):
         start_frames = None                                    # the combined task and a multi-clip env start from seeded random states
-    results = run_episodes(model, env, n_eval_episodes, start_frames, True, max_steps)
+    results = run_episodes(model, env, n_eval_episodes, start_frames, True, max_steps, compact)
     return dict({"global_step": int(global_step)}, **episode_statistics(results, max_ep_length(env)))
 
 

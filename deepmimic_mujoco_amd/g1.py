@@ -31,7 +31,8 @@ REASONS = {0: None, 1: "low_z", 2: "high_z", 3: "max_ep_len", 4: "acyclical_end"
 EXPORTS = ["dmg1_default_config", "dmg1_model_sizeof", "dmg1_create", "dmg1_destroy", "dmg1_last_error", "dmg1_load_clip",
            "dmg1_reset", "dmg1_step", "dmg1_step_forced", "dmg1_set_state", "dmg1_get_state", "dmg1_get_counters",
            "dmg1_set_counters", "dmg1_set_debug", "dmg1_last_kernel_ms", "dmg1_obs_dim", "dmg1_get_motion", "dmg1_set_motion",
-           "dmg1_set_seed", "dmg1_set_env_clips", "dmg1_get_env_clips", "dmg1_queue_counters"]
+           "dmg1_set_seed", "dmg1_set_env_clips", "dmg1_get_env_clips", "dmg1_queue_counters", "dmg1_step_active",
+           "dmg1_set_active_schedule"]
 
 _i32, _f64 = C.c_int32, C.c_double
 
@@ -163,6 +164,8 @@ def _lib():
         L.dmg1_reset.argtypes = [vp] * 5
         L.dmg1_step.argtypes = [vp] * 9
         L.dmg1_step_forced.argtypes = [vp] * 9
+        L.dmg1_step_active.argtypes = [vp, vp, vp, i32] + [vp] * 6
+        L.dmg1_set_active_schedule.argtypes = [vp, i32]
         L.dmg1_set_state.argtypes = [vp, vp, vp, vp, i32, vp]
         L.dmg1_get_state.argtypes = [vp] * 5
         L.dmg1_get_counters.argtypes = [vp] * 5
@@ -223,6 +226,15 @@ class G1HipEngine(EngineBase):
     def step(self, actions, out):
         assert actions.shape == (self.N, NACT) and actions.dtype == self.torch.float32 and actions.is_contiguous()
         super().step(actions, out)
+
+    def set_active_schedule(self, on=True):
+        """``step_active`` launches its slots longest-first (default, from 512 envs up) or in the list's order; same results."""
+        self._call("set_active_schedule", 1 if on else 0, stream=False)
+
+    def step_active(self, actions, env_ids, nslots, out):
+        assert actions.shape == (self.N, NACT) and actions.dtype == self.torch.float32 and actions.is_contiguous()
+        assert env_ids.dtype == self.torch.int32 and env_ids.is_contiguous() and env_ids.numel() >= int(nslots)
+        super().step_active(actions, env_ids, nslots, out)
 
     def step_forced(self, qpos, qvel, out):
         assert self._rows(qpos, qvel)

@@ -51,7 +51,8 @@ def build_parser():
     ap.add_argument("--eval-every", type=int, default=0, help="eval dashboard every N global steps (src/sb3_ppo.py:313 EVAL_N); 0 = off")
     ap.add_argument("--eval-envs", type=int, default=0,
                     help="> 0: batched deterministic evaluation (evaluation.py) on that many auto_reset=False envs on rank 0: at every "
-                         "--eval-every point (eval_batch.csv) and once after training (\"eval\" of the --json line); 0 = off")
+                         "--eval-every point (eval_batch.csv) and once after training (\"eval\" of the --json line); finished envs leave "
+                         "the launches on either robot (compact=\"all\"); 0 = off")
     ap.add_argument("--run-name", default="run")
     ap.add_argument("--eval-dir", default="~/deep_mimic")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],

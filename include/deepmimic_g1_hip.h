@@ -80,6 +80,24 @@ int dmg1_reset(DmG1Handle h, const uint8_t *mask, const int32_t *idx_init, float
 int dmg1_step(DmG1Handle h, const float *actions, float *obs, float *rew, uint8_t *done, float *terms, int32_t *reason,
               float *terminal_obs, void *stream);
 
+/* dmg1_step over a slot list, for runs in which envs drop out (evaluation.BatchEvaluator(compact="all")): the contract of
+ * dm_step_active (deepmimic_hip.h).  Slot s < nslots steps env env_ids[s] (device int32[>= nslots]); an entry outside
+ * [0, num_envs) — the -1 padding of dm_eval_advance — ends that slot's workgroup at once, in every launch of the step, so a padded
+ * list may be launched with an nslots that is only an upper bound of the live entries.  An env listed twice is a caller's error.  No
+ * auto-reset, whatever DmG1Config.auto_reset says: an env that is done keeps its terminal state (and its reset count), and an env
+ * that is not listed is not launched: its state row, counters, motion / clip slot and output rows are neither read nor written.
+ * actions, obs, rew, done, terms, reason are the full [num_envs, ...] arrays of dmg1_step, indexed by ENV; terms and reason may be
+ * NULL.  The pipeline is the one dmg1_step takes for the engine (DmG1Config.pipeline and num_envs), never a function of nslots:
+ * an env's trajectory does not depend on how many others are still listed, nor on the order of the list.  The grids are nslots
+ * workgroups (the pair kernel's persistent grid is sized from nslots).  From 512 envs up the listed envs are launched
+ * longest-first like dmg1_step's (the permuted list goes to a buffer of the engine; env_ids is only read).  The per-env work
+ * estimates behind that order are updated for the stepped envs only.  1 <= nslots <= num_envs; a null handle, actions, env_ids, obs,
+ * rew or done, or an nslots outside that range, returns DM_EINVAL, sets the dmg1_last_error text and launches nothing. */
+int dmg1_step_active(DmG1Handle h, const float *actions, const int32_t *env_ids, int nslots, float *obs, float *rew, uint8_t *done,
+                     float *terms, int32_t *reason, void *stream);
+/* on = 0: dmg1_step_active launches its slots in the caller's order (no longest-first pass); default 1.  Result-neutral. */
+int dmg1_set_active_schedule(DmG1Handle h, int on);
+
 /* Replaces DPEnv.step(action, force_state=(qpos, qvel)) (src/deepmimic_env.py:355-357).  qpos float[N*44], qvel float[N*43]. */
 int dmg1_step_forced(DmG1Handle h, const float *qpos, const float *qvel, float *obs, float *rew, uint8_t *done,
                      float *terms, int32_t *reason, void *stream);
@@ -111,11 +129,12 @@ int dmg1_set_motion(DmG1Handle h, const int32_t *motion, void *stream);
  *  list h <- (131 h + 97 geom1 + geom2 + 1) mod 2^24 (the oracle keeps the same: "stage_chash<k>") */
 int dmg1_set_debug(DmG1Handle h, float *debug);
 
-/* Diagnostics of the split pipeline: per round r = 0..5 of the LAST dmg1_step, host_out[4 r + 0 / 1 / 2] = tickets of
- * support-query pairs (MPR, plane-mesh), of analytic pairs, and tickets pulled.  Synchronises the device.  Zeros when monolithic. */
+/* Diagnostics of the split pipeline: per round r = 0..5 of the LAST dmg1_step or dmg1_step_active, whichever came last,
+ * host_out[4 r + 0 / 1 / 2] = tickets of support-query pairs (MPR, plane-mesh), of analytic pairs, and tickets pulled.
+ * Synchronises the device.  Zeros when monolithic. */
 int dmg1_queue_counters(DmG1Handle h, int32_t *host_out24);
 
-/* Kernel time of the last dmg1_step in ms (HIP events on the launch stream), or < 0. */
+/* Kernel time of the last dmg1_step or dmg1_step_active (whichever came last) in ms (HIP events on the launch stream), or < 0. */
 float dmg1_last_kernel_ms(DmG1Handle h);
 
 #ifdef __cplusplus
