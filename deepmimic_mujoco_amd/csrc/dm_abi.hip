@@ -372,10 +372,6 @@ static int launch(DmEngine *e, DmLaunch &P, int nslots, void *stream, int varian
   if (e->cfg.task == DM_TASK_COMBINED) {
     if (three_waves) hipLaunchKernelGGL(dm_step_combined_kernel_w3, grid, block, 0, s, P);
     else hipLaunchKernelGGL(dm_step_combined_kernel, grid, block, 0, s, P);
-#ifdef DM_EXPERIMENT_W4
-  } else if (e->waves == 4) {
-    hipLaunchKernelGGL(dm_step_kernel_w4, grid, block, 0, s, P);
-#endif
   } else if (three_waves) {
     // three waves per SIMD (168 VGPRs): faster than the two-wave build from 3 072 envs up since r2 (per-stage laundering of
     // the lane id: no hoisted lane-compare masks spilled across the stage loop): 13.4 vs 12.9 M at 4 096 envs, 21.4 vs

@@ -836,19 +836,12 @@ __device__ __forceinline__ bool ccd_eq(double a, double b) {
   a = fabs(a); b = fabs(b);
   return b > a ? ab < CCD_EPS * b : ab < CCD_EPS * a;
 }
-#ifdef G1_PAIRSTATS
-__device__ unsigned long long g_pairstats[8];   // 0 support evaluations, 1 tickets, 2 hint-separated, 3 contacts, 4 MPR misses
-#define PSTAT(k) do { if (lane == 0) atomicAdd(&g_pairstats[k], 1ull); } while (0)
-#else
-#define PSTAT(k) do {} while (0)
-#endif
 // support point of A - B in direction dir: both supports together, so the two hull scans share their memory round trips
 __device__ __forceinline__ void mpr_support(const Geo &a, const Geo &b, const double *dir, Sup &s, const int lane) {
   double nd[3] = {-dir[0], -dir[1], -dir[2]}, dla[3], dlb[3], pa[3], pb[3];
   drot_t(dla, a.mat, dir);
   drot_t(dlb, b.mat, nd);
   const bool ma = a.type == DM_GEOM_MESH, mb = b.type == DM_GEOM_MESH;
-  PSTAT(0);
 
   support_local(a, dla, pa);
   support_local(b, dlb, pb);
@@ -1062,7 +1055,6 @@ __device__ __forceinline__ int np_convex(Con *c, const Geo &a, const Geo &b, flo
     }
   }
   const int res = mpr_penetration(a, b, &depth, dir, pos, slot >= 0 ? hint : nullptr, sep, sep_valid, ps, lane);
-  PSTAT(1); if (res == -2) PSTAT(2); else if (res == 0) PSTAT(3); else PSTAT(4);
   if (cache && res == -1 && sep_valid) {   // remember what separated them (geom 1's frame)
     if (slot < 0) {
       if (direct) slot = 0;
@@ -3323,14 +3315,6 @@ extern "C" int dmg1_queue_counters(DmG1Handle e, int32_t *host_out24) {
   if (hipSetDevice(e->cfg.device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return DM_EHIP;
   return hipMemcpy(host_out24, e->dQctr, 24 * sizeof(int32_t), hipMemcpyDeviceToHost) == hipSuccess ? DM_OK : DM_EHIP;
 }
-#ifdef G1_PAIRSTATS
-extern "C" int dmg1_pairstats(unsigned long long *host_out8, int reset) {
-  hipDeviceSynchronize();
-  hipMemcpyFromSymbol(host_out8, HIP_SYMBOL(g1::g_pairstats), 8 * sizeof(unsigned long long));
-  if (reset) { unsigned long long z[8] = {}; hipMemcpyToSymbol(HIP_SYMBOL(g1::g_pairstats), z, sizeof z); }
-  return 0;
-}
-#endif
 extern "C" int dmg1_set_seed(DmG1Handle e, uint64_t seed) {
   if (!e) return DM_EINVAL;
   e->cfg.seed = seed;

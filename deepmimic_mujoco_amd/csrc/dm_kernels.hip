@@ -1755,10 +1755,109 @@ __device__ __forceinline__ float fwd_constraint(GDev &T, const int lane, const i
 // ======================================================================================
 // TASK 0: DPEnv (src/deepmimic_env.py).  TASK 1: DPCombinedEnv state machine (src/combined_env.py) on the same
 // physics; the state row's clip slot holds the motion id (0 walk, 1 run, 2 getup, 3 to_getup) and the idx slot n_steps.
+//
+// The functions in front of step_body are the phases of it that could be cut out with the same bits, registers, scratch and
+// speed: all but foot_contacts leave the four step kernels' code as it was, instruction for instruction (they hold no
+// floating-point arithmetic and take their scalars by value); foot_contacts makes them 5 .. 10 instructions shorter.  Every
+// other phase was cut out on its own and measured: it either moves the rounding (hipcc then picks other
+// products to contract into FMAs: the root-quaternion integration, get_obs together with calc_imitation_reward), raises the
+// scratch (write_outputs, the two terminations) or costs 0.6 .. 3.4 % of the step rate on some batch size (the RSI draw,
+// get_obs, calc_imitation_reward, the mode chain, the LDS init), so it stays inline in step_body.
+
+// The state row's qpos, qvel, qacc_warmstart and ctrl from LDS: the store-only exit of dm_set_state and the write-back
+__device__ __forceinline__ void store_state(float *st, const int lane) {
+  EnvLds &S = g_S;
+  if (lane < DMK_NQ) st[DMS_QPOS + lane] = S.qpos[lane];
+  if (lane < DMK_NV) { st[DMS_QVEL + lane] = S.qvel[lane]; st[DMS_WARM + lane] = S.warm[lane]; }
+  if (lane < DMK_NU) st[DMS_CTRL + lane] = S.ctrl[lane];
+}
+
+// mj_resetData after an instability, as MuJoCo does on the warning: physics mode and the MujocoException path of the task layer
+// (the caller clears the F8 foot bits: mj_resetData clears the contact array)
+__device__ __forceinline__ void reset_data(GDev &T, const int lane) {
+  EnvLds &S = g_S;
+  SYNC();
+  if (lane < DMK_NQ) S.qpos[lane] = T.qpos0[lane];
+  if (lane < DMK_NV) { S.qvel[lane] = 0; S.warm[lane] = 0; }
+  if (lane < DMK_NU) S.ctrl[lane] = 0;
+  SYNC();
+}
+
+// Which of the last evaluation's contacts are right foot / floor and left foot / floor, one contact per lane: the F8 update
+// and get_obs
+__device__ __forceinline__ void foot_contacts(GDev &T, const int lane, const int ncon, bool &rf, bool &lf) {
+  EnvLds &S = g_S;
+  rf = false; lf = false;
+  if (lane < ncon) {
+    const int g1 = S.c_g1[lane], g2 = S.c_g2[lane];
+    const bool fl = (g1 == T.floor_geom || g2 == T.floor_geom);
+    rf = fl && (g1 == T.rfoot_geom || g2 == T.rfoot_geom);
+    lf = fl && (g1 == T.lfoot_geom || g2 == T.lfoot_geom);
+  }
+}
+
+// The env's debug row (include/deepmimic_hip.h) from the last forward evaluation of the step proper
+__device__ __forceinline__ void write_debug_row(float *dbg, const int lane, const int ncon, const int nefc, const int solver_iter, const int nlimit,
+                                                const int overflow, const unsigned stage_ncon, const unsigned stage_nefc) {
+  EnvLds &S = g_S;
+  if (lane < 42) dbg[lane] = (&S.xpos[0][0])[lane];
+  if (lane < 48) dbg[42 + lane] = (&S.gpos[0][0])[lane];
+  for (int i = lane; i < 84; i += 64) dbg[90 + i] = (&S.cvel[0][0])[i];
+  if (lane < DMK_NV) { dbg[174 + lane] = S.qacc[lane]; dbg[208 + lane] = S.qacc_smooth[lane]; }
+  if (lane == 0) { dbg[242] = ncon; dbg[243] = nefc; dbg[244] = solver_iter; dbg[245] = nlimit; dbg[246] = overflow;
+                   dbg[247] = __int_as_float((int)stage_ncon); dbg[248] = __int_as_float((int)stage_nefc); }
+  if (lane < DMK_MAXCON) {
+    dbg[256 + 3 * lane] = (lane < ncon) ? (float)S.c_g1[lane] : -1.f;
+    dbg[257 + 3 * lane] = (lane < ncon) ? (float)S.c_g2[lane] : -1.f;
+    dbg[258 + 3 * lane] = (lane < ncon) ? S.c_dist[lane] : 0.f;
+  }
+}
+
+// One observation row (the step's obs, or info["terminal_observation"]): obs_a = obs[lane], obs_b = obs[64 + lane]
 template <int TASK>
-__device__ __forceinline__ void step_body(const DmLaunch &P) {
+__device__ __forceinline__ void store_obs(float *obs, const int env, const int lane, const float obs_a, const float obs_b) {
   constexpr int NOBS_T = TASK ? DM_NOBS_COMBINED : DM_NOBS;   // obs row stride
   constexpr int NOBS_B = NOBS_T - 64;                          // obs entries held by obs_b lanes
+  obs[(size_t)env * NOBS_T + lane] = obs_a;
+  if (lane < NOBS_B) obs[(size_t)env * NOBS_T + 64 + lane] = obs_b;
+}
+
+// mj_checkPos / mj_checkVel on the state in LDS: true if a position or velocity is not finite or beyond 1e10
+__device__ __forceinline__ bool check_pos_vel(const int lane) {
+  EnvLds &S = g_S;
+  const int lk = lane < DMK_NV ? lane : 0;
+  float a = (lane < DMK_NQ) ? S.qpos[lane] : 0.f, b = (lane < DMK_NV) ? S.qvel[lk] : 0.f;
+  return __any(!(fabsf(a) <= MAXVALF) || !(fabsf(b) <= MAXVALF));
+}
+
+// RK4 stage 0: X0 (after normalisation) and the empty accumulators into S.rk / S.rkq
+__device__ __forceinline__ void capture_x0(const int lane) {
+  EnvLds &S = g_S;
+  const int lk = lane < DMK_NV ? lane : 0;
+  if (lane < DMK_NV) {
+    const float v0 = S.qvel[lk];
+    S.rk[0][lk] = (lane < 3) ? S.qpos[lane] : ((lane >= 6) ? S.qpos[lane + 1] : 0.f);
+    S.rk[1][lk] = v0; S.rk[2][lk] = 0.f; S.rk[3][lk] = 0.f; S.rk[4][lk] = v0;
+  }
+  if (lane < 4) S.rkq[lane] = S.qpos[3 + lane];
+}
+
+// observation guard (:465-476): true if an entry of the observation is not finite or beyond obs_bound
+__device__ __forceinline__ bool obs_out_of_bounds(const DmLaunch &P, const float obs_a, const float obs_b) {
+  bool ob = !(fabsf(obs_a) <= P.obs_bound) || !(fabsf(obs_b) <= P.obs_bound);
+  return __any(ob);
+}
+
+// The state row's qpos, qvel, qacc_warmstart and ctrl into LDS
+__device__ __forceinline__ void load_state(const float *st, const int lane) {
+  EnvLds &S = g_S;
+  if (lane < DMK_NQ) S.qpos[lane] = st[DMS_QPOS + lane];
+  if (lane < DMK_NV) { S.qvel[lane] = st[DMS_QVEL + lane]; S.warm[lane] = st[DMS_WARM + lane]; }
+  if (lane < DMK_NU) S.ctrl[lane] = st[DMS_CTRL + lane];
+}
+
+template <int TASK>
+__device__ __forceinline__ void step_body(const DmLaunch &P) {
   constexpr int NTERMS = TASK ? 8 : 5;
   // Model tables are read from global memory at their use sites: 6 KB shared by every wave on the CU,
   // so they sit in the vector L1 / scalar cache; keeping them out of LDS leaves room for more envs.
@@ -1806,9 +1905,7 @@ __device__ __forceinline__ void step_body(const DmLaunch &P) {
   // F8 option (DmConfig.stale_contact_slots, src/deepmimic_env.py:88): mujoco-py hands the WHOLE contact array to the foot-contact
   // scan, so slots >= ncon still show what an earlier evaluation wrote.  One bit per slot and foot, kept in the state row.
   unsigned f8r = P.f8 ? (unsigned)sti[DMS_F8R] : 0u, f8l = P.f8 ? (unsigned)sti[DMS_F8L] : 0u;
-  if (lane < DMK_NQ) S.qpos[lane] = st[DMS_QPOS + lane];
-  if (lane < DMK_NV) { S.qvel[lane] = st[DMS_QVEL + lane]; S.warm[lane] = st[DMS_WARM + lane]; }
-  if (lane < DMK_NU) S.ctrl[lane] = st[DMS_CTRL + lane];
+  load_state(st, lane);
   SYNC();
   if (mode == DMK_MODE_STEP || mode == DMK_MODE_PHYSICS) {
     if (lane < DMK_NU) S.ctrl[lane] = P.actions[(size_t)env * DMK_NU + lane];  // ctrl = action * 1.0 (:347)
@@ -1858,14 +1955,11 @@ __device__ __forceinline__ void step_body(const DmLaunch &P) {
   int work = 0;                              // work estimate of this step (for longest-first scheduling)
 
   if (mode == DMK_MODE_SETSTATE && !P.run_forward) {  // store only
-    if (lane < DMK_NQ) st[DMS_QPOS + lane] = S.qpos[lane];
-    if (lane < DMK_NV) { st[DMS_QVEL + lane] = S.qvel[lane]; st[DMS_WARM + lane] = S.warm[lane]; }
-    if (lane < DMK_NU) st[DMS_CTRL + lane] = S.ctrl[lane];
+    store_state(st, lane);
     return;
   }
   if (mode == DMK_MODE_STEP || mode == DMK_MODE_FORCED || mode == DMK_MODE_PHYSICS) {  // mj_checkPos / mj_checkVel
-    float a = (lane < DMK_NQ) ? S.qpos[lane] : 0.f, b = (lane < DMK_NV) ? S.qvel[lk] : 0.f;
-    sim_err = __any(!(fabsf(a) <= MAXVALF) || !(fabsf(b) <= MAXVALF));
+    sim_err = check_pos_vel(lane);
   }
 
   PROF(0);
@@ -1878,24 +1972,13 @@ __device__ __forceinline__ void step_body(const DmLaunch &P) {
     GDev *Tp = (GDev *)P.T;
     asm volatile("" : "+s"(Tp));
     GDev &Ts = *Tp;
-#ifndef DM_NO_LANE_LAUNDER
     // the lane id is laundered per stage too: per-lane compares (lane == k, lane < n) are then recomputed inside the stage
     // (one v_cmp) instead of being hoisted out of the stage loop into SGPRs that spill to VGPR lanes (v_writelane / two
     // v_readlane per use)
     int lane_st = lane;
     asm volatile("" : "+v"(lane_st));
-#else
-    const int lane_st = lane;
-#endif
     fwd_smooth(Ts, lane_st);
-    if (it == 0) {  // capture X0 (after normalisation)
-      if (lane < DMK_NV) {
-        const float v0 = S.qvel[lk];
-        S.rk[0][lk] = (lane < 3) ? S.qpos[lane] : ((lane >= 6) ? S.qpos[lane + 1] : 0.f);
-        S.rk[1][lk] = v0; S.rk[2][lk] = 0.f; S.rk[3][lk] = 0.f; S.rk[4][lk] = v0;
-      }
-      if (lane < 4) S.rkq[lane] = S.qpos[3 + lane];
-    }
+    if (it == 0) capture_x0(lane);
     {
       const int cr = fwd_collide(Ts, lane_st);
       ncon = cr & 0xFF;
@@ -1908,13 +1991,8 @@ __device__ __forceinline__ void step_body(const DmLaunch &P) {
       // (rows weigh 16: measured, building the rows costs twice the sweeps on average; 4 .. 32 and a wide-path surcharge: +-0.3 %)
       work = (work >> 1) + 64 + (nefc > 0 ? 48 + 16 * nefc : 0) + nefc * solver_iter;
       if (P.f8) {   // every evaluation rewrites slots [0, ncon) of the contact array and leaves the rest
-        bool rfs = false, lfs = false;
-        if (lane < ncon) {
-          const int g1 = S.c_g1[lane], g2 = S.c_g2[lane];
-          const bool fl = (g1 == Ts.floor_geom || g2 == Ts.floor_geom);
-          rfs = fl && (g1 == Ts.rfoot_geom || g2 == Ts.rfoot_geom);
-          lfs = fl && (g1 == Ts.lfoot_geom || g2 == Ts.lfoot_geom);
-        }
+        bool rfs, lfs;
+        foot_contacts(Ts, lane, ncon, rfs, lfs);
         const unsigned keep = ncon >= 32 ? 0u : (~0u << ncon);
         f8r = (f8r & keep) | (unsigned)__ballot(rfs);
         f8l = (f8l & keep) | (unsigned)__ballot(lfs);
@@ -2000,11 +2078,7 @@ __device__ __forceinline__ void step_body(const DmLaunch &P) {
     if (mode == DMK_MODE_PHYSICS) {   // dm_physics_step: sim.step() alone; an instability resets the data as MuJoCo does
       if (sim_err) {
         f8r = f8l = 0;
-        SYNC();
-        if (lane < DMK_NQ) S.qpos[lane] = T.qpos0[lane];
-        if (lane < DMK_NV) { S.qvel[lane] = 0; S.warm[lane] = 0; }
-        if (lane < DMK_NU) S.ctrl[lane] = 0;
-        SYNC();
+        reset_data(T, lane);
       }
       break;
     }
@@ -2018,11 +2092,7 @@ __device__ __forceinline__ void step_body(const DmLaunch &P) {
       // MujocoException path (:366-378): zero obs, zero reward, done, empty info; MuJoCo resets mjData
       reward = 0; done = true; reason = DM_REASON_SIM_ERROR;
       f8r = f8l = 0;   // mj_resetData clears the contact array
-      SYNC();
-      if (lane < DMK_NQ) S.qpos[lane] = T.qpos0[lane];
-      if (lane < DMK_NV) { S.qvel[lane] = 0; S.warm[lane] = 0; }
-      if (lane < DMK_NU) S.ctrl[lane] = 0;
-      SYNC();
+      reset_data(T, lane);
     } else {
       // ---- get_obs (:33-45): qpos[7:], 0.1*qvel[6:], torso(8), foot contacts(2), phase(1)
       const float Sc = P.vel_obs_scale;
@@ -2040,13 +2110,8 @@ __device__ __forceinline__ void step_body(const DmLaunch &P) {
 #pragma unroll
       for (int i = 0; i < 8; i++)
         if (lane == 56 + i) obs_a = tor[i];
-      bool rf = false, lf = false;
-      if (lane < ncon) {
-        int g1 = S.c_g1[lane], g2 = S.c_g2[lane];
-        bool fl = (g1 == T.floor_geom || g2 == T.floor_geom);
-        rf = fl && (g1 == T.rfoot_geom || g2 == T.rfoot_geom);
-        lf = fl && (g1 == T.lfoot_geom || g2 == T.lfoot_geom);
-      }
+      bool rf, lf;
+      foot_contacts(T, lane, ncon, rf, lf);
       const float rff = (P.f8 ? f8r != 0 : __any(rf)) ? 1.f : 0.f, lff = (P.f8 ? f8l != 0 : __any(lf)) ? 1.f : 0.f;
       // TASK 1: motion length / frame of the current motion; to_getup is a 180-step pseudo clip whose target is
       // frame 1 of getup (MotionTransition getters, combined_env.py:67-99)
@@ -2156,28 +2221,15 @@ __device__ __forceinline__ void step_body(const DmLaunch &P) {
         ep_rew += reward;
         ep_len += 1;
         // ---- observation guard (:465-476)
-        bool ob = !(fabsf(obs_a) <= P.obs_bound) || !(fabsf(obs_b) <= P.obs_bound);
-        if (__any(ob)) {
+        if (obs_out_of_bounds(P, obs_a, obs_b)) {
           obs_a = 0; obs_b = 0; reward = 0; done = true; reason = DM_REASON_OBS_BOUNDS;
           for (int i = 0; i < 5; i++) terms[i] = 0;
           extra[0] = extra[1] = extra[2] = 0;
         }
       }
     }
-    if (P.debug && !after_reset) {
-      float *dbg = P.debug + (size_t)env * DM_DEBUG_STRIDE;
-      if (lane < 42) dbg[lane] = (&S.xpos[0][0])[lane];
-      if (lane < 48) dbg[42 + lane] = (&S.gpos[0][0])[lane];
-      for (int i = lane; i < 84; i += 64) dbg[90 + i] = (&S.cvel[0][0])[i];
-      if (lane < DMK_NV) { dbg[174 + lane] = S.qacc[lane]; dbg[208 + lane] = S.qacc_smooth[lane]; }
-      if (lane == 0) { dbg[242] = ncon; dbg[243] = nefc; dbg[244] = solver_iter; dbg[245] = nlimit; dbg[246] = overflow;
-                       dbg[247] = __int_as_float((int)stage_ncon); dbg[248] = __int_as_float((int)stage_nefc); }
-      if (lane < DMK_MAXCON) {
-        dbg[256 + 3 * lane] = (lane < ncon) ? (float)S.c_g1[lane] : -1.f;
-        dbg[257 + 3 * lane] = (lane < ncon) ? (float)S.c_g2[lane] : -1.f;
-        dbg[258 + 3 * lane] = (lane < ncon) ? S.c_dist[lane] : 0.f;
-      }
-    }
+    if (P.debug && !after_reset)
+      write_debug_row(P.debug + (size_t)env * DM_DEBUG_STRIDE, lane, ncon, nefc, solver_iter, nlimit, overflow, stage_ncon, stage_nefc);
     if (task_pass) {
       if (P.rew && lane == 0) P.rew[env] = reward;
       if (P.done && lane == 0) P.done[env] = done ? 1 : 0;
@@ -2187,10 +2239,7 @@ __device__ __forceinline__ void step_body(const DmLaunch &P) {
                                              : (lane == 4) ? terms[4] : (lane == 5) ? extra[0] : (lane == 6) ? extra[1] : extra[2];
       if (done && P.auto_reset && mode == DMK_MODE_STEP) {
         // VecEnv worker: info["terminal_observation"] = obs; obs = env.reset()
-        if (P.terminal_obs) {
-          P.terminal_obs[(size_t)env * NOBS_T + lane] = obs_a;
-          if (lane < NOBS_B) P.terminal_obs[(size_t)env * NOBS_T + 64 + lane] = obs_b;
-        }
+        if (P.terminal_obs) store_obs<TASK>(P.terminal_obs, env, lane, obs_a, obs_b);
         int fi;
         if (TASK) {  // DPCombinedEnv.reset(rsi=True) (:219-227)
           motion = (dm_hash32(P.seed, env, rcnt, 0x5EED) & 1) ? 2 : 0;
@@ -2215,10 +2264,7 @@ __device__ __forceinline__ void step_body(const DmLaunch &P) {
         continue;  // one more forward evaluation at the reset state (set_state -> sim.forward)
       }
     }
-    if (P.obs) {
-      P.obs[(size_t)env * NOBS_T + lane] = obs_a;
-      if (lane < NOBS_B) P.obs[(size_t)env * NOBS_T + 64 + lane] = obs_b;
-    }
+    if (P.obs) store_obs<TASK>(P.obs, env, lane, obs_a, obs_b);
     break;
   }
 
@@ -2231,9 +2277,7 @@ __device__ __forceinline__ void step_body(const DmLaunch &P) {
     if (lane < 4) P.debug[(size_t)env * DM_DEBUG_STRIDE + 368 + lane] = (float)g_S.prof_stage[lane]; }
 #endif
   // ---------------------------------------------------------------- state write-back
-  if (lane < DMK_NQ) st[DMS_QPOS + lane] = S.qpos[lane];
-  if (lane < DMK_NV) { st[DMS_QVEL + lane] = S.qvel[lane]; st[DMS_WARM + lane] = S.warm[lane]; }
-  if (lane < DMK_NU) st[DMS_CTRL + lane] = S.ctrl[lane];
+  store_state(st, lane);
   if (lane == 0) { sti[DMS_IDX] = idx_curr; sti[DMS_EPLEN] = ep_len; st[DMS_EPREW] = ep_rew; sti[DMS_RCNT] = rcnt; }
   if (TASK && lane == 0) sti[DMS_CLIP] = motion;
   if (P.f8 && lane == 0) { sti[DMS_F8R] = (int)f8r; sti[DMS_F8L] = (int)f8l; }
@@ -2254,12 +2298,6 @@ extern "C" __global__ void __launch_bounds__(64 * DMK_ENVS_PER_BLOCK, 3) dm_step
 extern "C" __global__ void __launch_bounds__(64 * DMK_ENVS_PER_BLOCK, 3) dm_step_combined_kernel_w3(DmLaunch P) {
   step_body<1>(P);
 }
-#ifdef DM_EXPERIMENT_W4
-// Experiment: four waves per SIMD = 128 VGPRs.  Never selected by dm_step; DM_WAVES=4 forces it.
-extern "C" __global__ void __launch_bounds__(64 * DMK_ENVS_PER_BLOCK, 4) dm_step_kernel_w4(DmLaunch P) {
-  step_body<0>(P);
-}
-#endif
 
 // Uniform random actions in [-2, 2) for bench.py config 2 (same generator as the oracle driver).
 extern "C" __global__ void dm_fill_actions_kernel(float *actions, int n, uint64_t seed, uint32_t step) {

@@ -26,7 +26,7 @@ REGIONS = (
     ("fwd_smooth_other", r"float fwd_smooth\(", r"float euler_damped_solve\("),
     ("build_row", r"void build_row\(", r"float fwd_constraint_wide\("),
     ("fwd_constraint_wide", r"float fwd_constraint_wide\(", r"float fwd_constraint\("),
-    ("fwd_constraint", r"float fwd_constraint\(", r"void step_body\("),
+    ("fwd_constraint", r"float fwd_constraint\(", r"void store_state\("),
 )
 USES = ("v_fma_f32", "v_fmac_f32", "v_mul_f32", "v_rcp_f32")
 
