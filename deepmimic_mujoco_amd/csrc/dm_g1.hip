@@ -2826,6 +2826,7 @@ struct DmG1Engine {
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   bool timed = false;
   bool active_lpt = true;   // dmg1_step_active orders its slot list longest-first (from 512 envs up, as dmg1_step)
+  int skip = 0;             // Launch::pad of every launch: 256 (dmg1_set_null_cache) hands np_convex of the monolithic kernel a null cache
   // split pipeline (dmg1_step of batches >= 512 envs, or DmG1Config.pipeline = 2)
   bool split = false;
   char *dWs = nullptr;
@@ -3197,6 +3198,7 @@ static int g1_launch(DmG1Engine *e, g1::Launch &P, void *stream, bool time_it, c
   if (e->cfg.task && (e->L[1] < 1 || e->L[2] < 2)) return g1_fail(e, DM_EINVAL, "combined task needs clips 0, 1, 2 = walk, run, getup");
   if (hipSetDevice(e->cfg.device) != hipSuccess) return g1_fail(e, DM_EHIP, "hipSetDevice failed");
   bool lpt = true;
+  P.pad = e->skip;
 #ifdef G1_PROFILE   // phase switches of the diagnostic build only: the shipped library never reads the environment on a launch
   if (const char *sk = getenv("DMG1_SKIP")) P.pad = atoi(sk);   // bit 0 no PGS sweeps, 1 no collision, 2 no A matrix, 3 no rows, 4 no constraint solve
   lpt = !getenv("DMG1_NO_LPT");
@@ -3336,6 +3338,27 @@ extern "C" int dmg1_get_env_clips(DmG1Handle e, int32_t *clip_ids, void *stream)
 extern "C" int dmg1_set_debug(DmG1Handle e, float *debug) {
   if (!e) return DM_EINVAL;
   e->dDebug = debug;
+  return DM_OK;
+}
+extern "C" int dmg1_set_null_cache(DmG1Handle e, int on) {
+  if (!e) return DM_EINVAL;
+  e->skip = on ? 256 : 0;
+  return DM_OK;
+}
+extern "C" int dmg1_sep_cache_entries(DmG1Handle e, int32_t *host_out2) {
+  if (!e || !host_out2) return DM_EINVAL;
+  host_out2[0] = host_out2[1] = 0;
+  if (hipSetDevice(e->cfg.device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return DM_EHIP;
+  const size_t per_env = 4 * g1::SEPC + 4;
+  std::vector<int32_t> h((size_t)e->N * per_env);
+  if (hipMemcpy(h.data(), e->dSepc, h.size() * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess) return DM_EHIP;
+  for (int env = 0; env < e->N; env++)
+    for (int k = 0; k < g1::SEPC; k++) host_out2[0] += h[env * per_env + 4 * k] >= 0;
+  if (e->split && e->dSepc2) {
+    h.resize((size_t)e->N * 1024 * 4);
+    if (hipMemcpy(h.data(), e->dSepc2, h.size() * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess) return DM_EHIP;
+    for (size_t k = 0; k < (size_t)e->N * 1024; k++) host_out2[1] += h[4 * k] >= 0;
+  }
   return DM_OK;
 }
 extern "C" float dmg1_last_kernel_ms(DmG1Handle e) {

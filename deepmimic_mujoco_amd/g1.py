@@ -32,7 +32,7 @@ EXPORTS = ["dmg1_default_config", "dmg1_model_sizeof", "dmg1_create", "dmg1_dest
            "dmg1_reset", "dmg1_step", "dmg1_step_forced", "dmg1_set_state", "dmg1_get_state", "dmg1_get_counters",
            "dmg1_set_counters", "dmg1_set_debug", "dmg1_last_kernel_ms", "dmg1_obs_dim", "dmg1_get_motion", "dmg1_set_motion",
            "dmg1_set_seed", "dmg1_set_env_clips", "dmg1_get_env_clips", "dmg1_queue_counters", "dmg1_step_active",
-           "dmg1_set_active_schedule"]
+           "dmg1_set_active_schedule", "dmg1_set_null_cache", "dmg1_sep_cache_entries"]
 
 _i32, _f64 = C.c_int32, C.c_double
 
@@ -171,6 +171,8 @@ def _lib():
         L.dmg1_get_counters.argtypes = [vp] * 5
         L.dmg1_set_counters.argtypes = [vp] * 4
         L.dmg1_set_debug.argtypes = [vp, vp]
+        L.dmg1_set_null_cache.argtypes = [vp, i32]
+        L.dmg1_sep_cache_entries.argtypes = [vp, vp]
         L.dmg1_set_seed.argtypes = [vp, C.c_uint64]
         L.dmg1_set_env_clips.argtypes = [vp, vp, vp]
         L.dmg1_get_env_clips.argtypes = [vp, vp, vp]
@@ -269,6 +271,16 @@ class G1HipEngine(EngineBase):
 
     def last_kernel_ms(self):
         return float(self.L.dmg1_last_kernel_ms(self.h))
+
+    def set_null_cache(self, on=True):
+        """Test hook: the monolithic kernel runs MPR without its separating-direction cache from the next launch on."""
+        self._call("set_null_cache", 1 if on else 0, stream=False)
+
+    def sep_cache_entries(self):
+        """Test hook: live entries of the (monolithic kernel's, pair kernel's) separating-direction cache."""
+        buf = (C.c_int32 * 2)()
+        self._call("sep_cache_entries", buf, stream=False)
+        return int(buf[0]), int(buf[1])
 
     def queue_counters(self):
         """split pipeline: per round of the last step (support-query pair tickets, analytic pair tickets, tickets pulled)."""

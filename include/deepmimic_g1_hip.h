@@ -134,6 +134,14 @@ int dmg1_set_debug(DmG1Handle h, float *debug);
  * Synchronises the device.  Zeros when monolithic. */
 int dmg1_queue_counters(DmG1Handle h, int32_t *host_out24);
 
+/* Test hooks of the separating-direction cache of the MPR pairs (result-neutral by design; tests/test_g1_pair_cover_gpu.py).
+ * dmg1_set_null_cache: on != 0 makes every later launch of the monolithic kernel run np_convex without its cache (the pair
+ * kernel of the split pipeline keeps its own).  dmg1_sep_cache_entries: host_out[0] = live entries (pair id >= 0) of the
+ * monolithic kernel's 16-entry-per-env cache, host_out[1] = of the split pipeline's one-entry-per-(env, pair) cache (0 when
+ * monolithic).  Synchronises the device. */
+int dmg1_set_null_cache(DmG1Handle h, int on);
+int dmg1_sep_cache_entries(DmG1Handle h, int32_t *host_out2);
+
 /* Kernel time of the last dmg1_step or dmg1_step_active (whichever came last) in ms (HIP events on the launch stream), or < 0. */
 float dmg1_last_kernel_ms(DmG1Handle h);
 
