@@ -13,6 +13,7 @@
 // (oracle/dm_oracle.c) is an independent scalar implementation of the same spec.
 #include "../../include/deepmimic_hip.h"
 #include "dm_device.h"
+#include "dm_math.h"
 #include "dm_rng.h"
 #include "dm_topology.h"
 
@@ -75,21 +76,6 @@ typedef const __attribute__((address_space(1))) char GByte;
 
 namespace {
 
-// Compile-time loop with early exit: f(integral_constant<int, I>) returns false to stop.  Guarantees
-// static register indices for the per-lane A-matrix row (a rolled loop would put it in scratch).
-template <int I, int N>
-struct StaticFor {
-  template <class F>
-  static __device__ __forceinline__ void run(F &&f) {
-    if constexpr (I < N) {
-      if (f(std::integral_constant<int, I>{})) StaticFor<I + 1, N>::run(f);
-    }
-  }
-};
-
-__device__ __forceinline__ float rl(float v, int lane) {
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane));
-}
 // a where the lane's bit is set in the compile-time lane mask, b elsewhere: one v_cndmask with the mask in SGPRs
 // (a per-lane bit test would cost three VALU instructions)
 template <unsigned long long MASK>
@@ -213,18 +199,6 @@ __device__ __forceinline__ void load_factor_row(lds_cfloat_p Sp, float (&W)[DMK_
     load_factor_row<I, K + 1>(Sp, W, dinv);
   }
 }
-template <int CTRL>
-__device__ __forceinline__ float dpp_mov(float v) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true));
-}
-// sum over the 64 lanes, result uniform in every lane
-__device__ __forceinline__ float wave_sum(float v) {
-  v += dpp_mov<0xB1>(v);   // quad_perm [1,0,3,2]
-  v += dpp_mov<0x4E>(v);   // quad_perm [2,3,0,1]
-  v += dpp_mov<0x141>(v);  // row_half_mirror
-  v += dpp_mov<0x140>(v);  // row_mirror
-  return (rl(v, 0) + rl(v, 16)) + (rl(v, 32) + rl(v, 48));
-}
 __device__ __forceinline__ unsigned long long lanemask_lt(int lane) {
   return (lane == 0) ? 0ull : (~0ull >> (64 - lane));
 }
@@ -234,20 +208,6 @@ __device__ __forceinline__ int prefix_count(bool flag, int lane, int *total) {
   return __popcll(m & lanemask_lt(lane));
 }
 
-__device__ __forceinline__ void cross3(float *r, const float *a, const float *b) {
-  float x = a[1] * b[2] - a[2] * b[1], y = a[2] * b[0] - a[0] * b[2], z = a[0] * b[1] - a[1] * b[0];
-  r[0] = x; r[1] = y; r[2] = z;
-}
-__device__ __forceinline__ float dot3(const float *a, const float *b) {
-  return a[0] * b[0] + a[1] * b[1] + a[2] * b[2];
-}
-__device__ __forceinline__ void quat_mul(float *r, const float *a, const float *b) {
-  float w = a[0] * b[0] - a[1] * b[1] - a[2] * b[2] - a[3] * b[3];
-  float x = a[0] * b[1] + a[1] * b[0] + a[2] * b[3] - a[3] * b[2];
-  float y = a[0] * b[2] - a[1] * b[3] + a[2] * b[0] + a[3] * b[1];
-  float z = a[0] * b[3] + a[1] * b[2] - a[2] * b[1] + a[3] * b[0];
-  r[0] = w; r[1] = x; r[2] = y; r[3] = z;
-}
 __device__ __forceinline__ void quat_rot(float *r, const float *q, const float *v) {
   float t[3], u[3];
   cross3(t, q + 1, v);
@@ -256,23 +216,6 @@ __device__ __forceinline__ void quat_rot(float *r, const float *q, const float *
   r[0] = v[0] + q[0] * t[0] + u[0];
   r[1] = v[1] + q[0] * t[1] + u[1];
   r[2] = v[2] + q[0] * t[2] + u[2];
-}
-__device__ __forceinline__ void quat2mat(float *m, const float *q) {
-  float w = q[0], x = q[1], y = q[2], z = q[3];
-  m[0] = w * w + x * x - y * y - z * z; m[1] = 2 * (x * y - w * z); m[2] = 2 * (x * z + w * y);
-  m[3] = 2 * (x * y + w * z); m[4] = w * w - x * x + y * y - z * z; m[5] = 2 * (y * z - w * x);
-  m[6] = 2 * (x * z - w * y); m[7] = 2 * (y * z + w * x); m[8] = w * w - x * x - y * y + z * z;
-}
-__device__ __forceinline__ void quat_normalize(float *q) {
-  float n = sqrtf(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-  if (n < MINVALF) { q[0] = 1; q[1] = q[2] = q[3] = 0; }
-  else { float i = 1.0f / n; q[0] *= i; q[1] *= i; q[2] *= i; q[3] *= i; }
-}
-__device__ __forceinline__ void mat_vec(float *r, const float *m, const float *v) {
-  float x = m[0] * v[0] + m[1] * v[1] + m[2] * v[2];
-  float y = m[3] * v[0] + m[4] * v[1] + m[5] * v[2];
-  float z = m[6] * v[0] + m[7] * v[1] + m[8] * v[2];
-  r[0] = x; r[1] = y; r[2] = z;
 }
 __device__ __forceinline__ void mat_t_vec(float *r, const float *m, const float *v) {
   float x = m[0] * v[0] + m[3] * v[1] + m[6] * v[2];
@@ -305,14 +248,6 @@ __device__ __forceinline__ void cross_force(float *r, const float *vel, const fl
   r[3] = c[0]; r[4] = c[1]; r[5] = c[2];
 }
 __device__ __forceinline__ float clampf(float x, float lo, float hi) { return fminf(fmaxf(x, lo), hi); }
-
-// py3dtf.Quaternion(x,y,z,w).to_rpy() restated: standard ZYX, no normalisation
-__device__ __forceinline__ void quat_to_rpy(const float *q, float *rpy) {
-  float w = q[0], x = q[1], y = q[2], z = q[3];
-  rpy[0] = atan2f(2 * (w * x + y * z), 1 - 2 * (x * x + y * y));
-  rpy[1] = asinf(clampf(2 * (w * y - z * x), -1.f, 1.f));
-  rpy[2] = atan2f(2 * (w * z + x * y), 1 - 2 * (y * y + z * z));
-}
 
 // ---------------------------------------------------------------- narrowphase (per lane)
 // up to 4 candidate contacts per lane in registers (static slots)

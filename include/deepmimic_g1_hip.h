@@ -126,7 +126,26 @@ int dmg1_set_motion(DmG1Handle h, const int32_t *motion, void *stream);
  *  [0:117) xpos | [117:160) qacc_smooth | [160:203) qacc | 203 ncon | 204 nefc | 205 solver_iter | 206 nlimit | 207 overflow |
  *  [208:208+48*9) per contact: dist, geom1, geom2, pos3, normal3 | [640:640+256) efc_force |
  *  after a step, per RK stage k = 0..3: 1000+k contacts, 1004+k rows (low byte), 1012+k a 24-bit hash of the stage's contact
- *  list h <- (131 h + 97 geom1 + geom2 + 1) mod 2^24 (the oracle keeps the same: "stage_chash<k>") */
+ *  list h <- (131 h + 97 geom1 + geom2 + 1) mod 2^24 (the oracle keeps the same: "stage_chash<k>") |
+ *  1008 broadphase survivors, 1009 / 1010 / 1011 of them analytic, plane - mesh and MPR pairs |
+ *  [900:916) per-phase clock sums of the diagnostic build (-DG1_PROFILE) */
+#define DMG1_DBG_XPOS 0
+#define DMG1_DBG_QACC_SMOOTH 117
+#define DMG1_DBG_QACC 160
+#define DMG1_DBG_NCON 203
+#define DMG1_DBG_NEFC 204
+#define DMG1_DBG_SOLVER_ITER 205
+#define DMG1_DBG_NLIMIT 206
+#define DMG1_DBG_OVERFLOW 207
+#define DMG1_DBG_CONTACT 208        /* DMG1_MAXCON records of DMG1_DBG_CONTACT_STRIDE floats */
+#define DMG1_DBG_CONTACT_STRIDE 9
+#define DMG1_DBG_EFC_FORCE 640      /* DMG1_MAXROW floats */
+#define DMG1_DBG_PROF 900
+#define DMG1_DBG_STAGE_NCON 1000
+#define DMG1_DBG_STAGE_NEFC 1004
+#define DMG1_DBG_NSURV 1008
+#define DMG1_DBG_PAIR_CLASS 1009    /* analytic, plane - mesh, MPR */
+#define DMG1_DBG_STAGE_CHASH 1012
 int dmg1_set_debug(DmG1Handle h, float *debug);
 
 /* Diagnostics of the split pipeline: per round r = 0..5 of the LAST dmg1_step or dmg1_step_active, whichever came last,

@@ -20,7 +20,7 @@
  * half of the trials.  Real MuJoCo makes that choice by the rounding of its own build, so neither value is "MuJoCo's";
  * a parity check against ANY second implementation needs a rule that does not depend on the last bit: support values
  * within 1e-12 m of the maximum are tied and the lowest vertex index wins (box corners / cylinder caps: the positive
- * side).  The HIP engine applies the same rule (csrc/dm_g1.hip: scan4_pick / wave_pick / support_local).
+ * side).  The HIP engine applies the same rule (csrc/dm_g1_narrow.h: scan4_pick / wave_pick / support_local).
  */
 #ifndef DM_CONVEX_H
 #define DM_CONVEX_H

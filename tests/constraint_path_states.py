@@ -13,7 +13,7 @@ GPU, no test in here; tests/test_constraint_paths_cpu.py asserts the quotas, tes
 import numpy as np
 
 MAXCON, MAXROW = 32, 128            # DMK_MAXCON, DMK_MAXROW (csrc/dm_kernels.hip)
-G1_MAXCON, G1_MAXROW = 48, 256      # MAXCON, MAXROW (csrc/dm_g1.hip)
+G1_MAXCON, G1_MAXROW = 48, 256      # MAXCON, MAXROW (csrc/dm_g1_device.h)
 TIE_DIST, TIE_LIMIT = 2e-5, 1e-5
 BOUNDARY_NEFC = (0, 1, 7, 8, 9, 31, 32, 33, 63, 64, 65)
 TOP_NEFC = (127, 128)

@@ -1,4 +1,4 @@
-"""Single-step cases for the task layer of the Unitree G1 engine (csrc/dm_g1.hip: step_enter, task_and_finish, the in-kernel
+"""Single-step cases for the task layer of the Unitree G1 engine (csrc/dm_g1_task.h: step_enter, task_and_finish, the in-kernel
 auto-reset), for DPEnv(robot="unitree_g1") and DPCombinedEnv().  A plain module: it builds the cases, runs them on the fp64
 oracle and restates the RSI draw; it touches no GPU and holds no test.  tests/test_g1_task_cases_cpu.py proves on the oracle alone
 that every case reaches the branch it names; tests/test_g1_task_layer_gpu.py runs the same cases on the engine.

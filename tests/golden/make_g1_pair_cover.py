@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Writes tests/golden/g1_pair_cover.npz: Unitree G1 poses that between them put (nearly) every collision pair of the model into
 contact, with the fp64 oracle's answer for each.  tests/test_g1_pair_cover_cpu.py re-derives every stored number on the oracle;
-tests/test_g1_pair_cover_gpu.py holds the HIP narrowphase (csrc/dm_g1.hip) to them.  CPU only, seeded, about ten minutes on one
+tests/test_g1_pair_cover_gpu.py holds the HIP narrowphase (csrc/dm_g1_narrow.h) to them.  CPU only, seeded, about ten minutes on one
 core:
 
     python tests/golden/make_g1_pair_cover.py            # writes tests/golden/g1_pair_cover.npz
@@ -62,7 +62,7 @@ def type_class(g, g1, g2):
 
 
 def is_mpr(g, g1, g2):
-    """pair_class(t1, t2) == 2 of csrc/dm_g1.hip: everything that is neither plane-x, sphere-sphere, sphere-box nor box-box."""
+    """pair_class(t1, t2) == 2 of csrc/dm_g1_narrow.h: everything that is neither plane-x, sphere-sphere, sphere-box nor box-box."""
     t1, t2 = int(g.geom_type[g1]), int(g.geom_type[g2])
     return not (t1 == 0 or (t1 == 2 and t2 in (2, 6)) or (t1 == 6 and t2 == 6))
 

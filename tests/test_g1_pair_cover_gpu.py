@@ -1,4 +1,4 @@
-"""The G1 collision path (csrc/dm_g1.hip: broadphase with its oriented-box and box-above-plane filters, the eight analytic
+"""The G1 collision path (csrc/dm_g1_narrow.h: broadphase with its oriented-box and box-above-plane filters, the eight analytic
 routines, MPR with the cluster-culled mesh support map and the separating-direction cache) on the states of
 tests/golden/g1_pair_cover.npz, which between them touch every collision pair the search could reach, plus near-miss twins.  The
 fp64 oracle's answers come from the fixture (tests/test_g1_pair_cover_cpu.py ties them to the live oracle); no state is left out

@@ -1,4 +1,4 @@
-"""The task layer of the Unitree G1 engine (csrc/dm_g1.hip: step_enter, task_and_finish, the in-kernel auto-reset) against the fp64
+"""The task layer of the Unitree G1 engine (csrc/dm_g1_task.h: step_enter, task_and_finish, the in-kernel auto-reset) against the fp64
 oracle on every exit path, for DPEnv(robot="unitree_g1") and DPCombinedEnv(), through both pipelines.  The cases come from
 tests/g1_task_cases.py; tests/test_g1_task_cases_cpu.py proves on the oracle alone that they reach what they name.
 
