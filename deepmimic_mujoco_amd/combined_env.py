@@ -247,11 +247,12 @@ class HipCombinedVecEnv(HipBatchEnv):
     def __new__(cls, num_envs, robot="unitree_g1", getup_motion="getup_facedown", device=0, seed=1234, auto_reset=True, **kw):
         if robot == "unitree_g1" and cls is HipCombinedVecEnv:
             from .g1 import HipG1CombinedVecEnv
-            return HipG1CombinedVecEnv(num_envs, device=device, seed=seed, auto_reset=auto_reset, sub_batches=kw.get("sub_batches", 1))
+            return HipG1CombinedVecEnv(num_envs, device=device, seed=seed, auto_reset=auto_reset, sub_batches=kw.get("sub_batches", 1),
+                                       integrator=kw.get("integrator"))
         return super().__new__(cls)
 
     def __init__(self, num_envs, robot="unitree_g1", getup_motion="getup_facedown", device=0, seed=1234,
-                 auto_reset=True):
+                 auto_reset=True, integrator=None):
         self.robot_config = RobotConfig(robot)
         model, cfg = load_model(self.robot_config.xml_path), self.ENV_CFG
 
@@ -259,7 +260,7 @@ class HipCombinedVecEnv(HipBatchEnv):
             e = _lib.HipEngine(model, nk, device=device, seed=seed, auto_reset=auto_reset,
                                task=_lib.TASK_COMBINED, max_ep_length=cfg.MAX_EP_LENGTH,
                                vel_obs_scale=cfg.VEL_OBS_SCALE, low_z=self.robot_config.low_z,
-                               amnesty_steps=cfg.AMNESTY_STEPS, to_getup_len=MTToGetup.length)
+                               amnesty_steps=cfg.AMNESTY_STEPS, to_getup_len=MTToGetup.length, integrator=integrator)
             self.clips = _load_clips(e, model, robot, getup_motion)
             return e
         super().__init__(num_envs, 1, make, model, NOBS_COMBINED, 8, NU, infos=_LazyCombinedInfos)   # one engine: no sub_batches here

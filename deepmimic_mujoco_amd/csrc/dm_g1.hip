@@ -17,7 +17,7 @@
 //   dm_g1_dynamics.h    kinematics .. fwd_smooth, integrate_pos
 //   dm_g1_narrow.h      broadphase, narrowphase of one pair
 //   dm_g1_constraint.h  constraint rows, projection, PGS
-//   dm_g1_task.h        step_enter, rk_advance, task_and_finish, step_write_back
+//   dm_g1_task.h        step_enter, rk_advance / euler_advance, task_and_finish, step_write_back
 #include "dm_g1_device.h"
 #include "dm_g1_math.h"
 #include "dm_g1_dynamics.h"
@@ -83,12 +83,15 @@ __device__ __noinline__ int collide(const Dev &T, const Launch &P, const int env
 // One forward evaluation = a per-env first half (poses, inertia, factorisation, smooth dynamics), the collision stage, and a
 // per-env second half (constraint rows, A, PGS).  The monolithic kernel runs all three on the env's wave; the split pipeline runs
 // the halves in g1_env_kernel and the narrowphase of ALL envs' pairs in g1_pair_kernel (one wave per pair).
-__device__ __forceinline__ void forward_pre(const Dev &T, const int lane, const bool qlo) {
+// EULER: the kernels of the Euler integrator, which keep the unfactored M (park_m) for the step's second factorisation.
+template <bool EULER>
+__device__ __forceinline__ void forward_pre(const Launch &P, const Dev &T, const int env, const int lane, const bool qlo) {
   PROF(15);
   kinematics(T, lane, qlo);
   com_pos(T, lane);
   PROF(0);
   crb_factor(T, lane);
+  if constexpr (EULER) park_m(P, T, env, lane);
   PROF(1);
   fwd_smooth(T, lane);   // before the collision stage: its scratch shares LDS with the contact arrays
   PROF(2);
@@ -117,16 +120,20 @@ __device__ __forceinline__ void forward_post(const Launch &P, const Dev &T, cons
   else fwd_constraint(T, JT, BT, AR, RW, nefc, lane, (P.skip & SKIP_PGS) ? 0 : T.iterations);
   PROF(10);
 }
+template <bool EULER>
 __device__ __noinline__ void forward(const Launch &P, const Dev &T, const int env, const int lane, const bool qlo) {
-  forward_pre(T, lane, qlo);
+  forward_pre<EULER>(P, T, env, lane, qlo);
   int ncon = 0;
   if (!(P.skip & SKIP_COLLIDE)) ncon = collide(T, P, env, lane);
   else { if (lane == 0) { S.info[0] = 0; S.info[4] = 0; } SYNC(); }
   forward_post<false>(P, T, env, lane, ncon);
 }
 
-// The monolithic kernel: one wave runs the whole step (or the single evaluation of the other modes) of its env.
-extern "C" __global__ void __launch_bounds__(64, 2) g1_step_kernel(Launch P) {
+// The monolithic kernel: one wave runs the whole step (or the single evaluation of the other modes) of its env.  The integrator is a
+// template argument and each has its own kernels (g1_step_kernel / g1_step_euler_kernel, g1_env_kernel / g1_env_euler_kernel): the
+// RK4 kernels keep the register allocation and scratch they had before the Euler option existed.
+template <bool EULER>
+__device__ __forceinline__ void step_kernel_body(const Launch &P) {
   const int lane = threadIdx.x;
   if ((int)blockIdx.x >= P.nslots) return;
   const int env = (P.order && P.mode == MODE_STEP) ? P.order[blockIdx.x] : (int)blockIdx.x;
@@ -141,10 +148,10 @@ extern "C" __global__ void __launch_bounds__(64, 2) g1_step_kernel(Launch P) {
   if (!step_enter(P, T, env, lane, X)) return;
   for (;;) {
     if (!X.sim_err) {
-      forward(P, T, env, lane, mode == MODE_STEP && !X.after_reset && X.stage > 0);   // the only call site: the evaluation is ~20 k instructions
+      forward<EULER>(P, T, env, lane, mode == MODE_STEP && !X.after_reset && X.stage > 0);   // the only call site: the evaluation is ~20 k instructions
       X.work += 4000 + S.info[1] * (8 + 6 * S.info[3]) + 3000 * ((S.info[6] >> 16) & 0xFF);   // fixed part, rows x sweeps, MPR pairs
       if (mode == MODE_STEP && !X.after_reset) {
-        if (rk_advance(P, T, env, lane, X)) continue;
+        if (EULER ? euler_advance(P, T, env, lane, X) : rk_advance(P, T, env, lane, X)) continue;
       } else if (mode == MODE_FORCED && !X.after_reset) {
         const bool badv = (lane < NV) && !(fabsf(S.qacc[lane]) <= MAXVALF);
         X.sim_err = __any(badv);
@@ -160,6 +167,8 @@ extern "C" __global__ void __launch_bounds__(64, 2) g1_step_kernel(Launch P) {
 #endif
   step_write_back(P, env, lane, X);
 }
+extern "C" __global__ void __launch_bounds__(64, 2) g1_step_kernel(Launch P) { step_kernel_body<false>(P); }
+extern "C" __global__ void __launch_bounds__(64, 2) g1_step_euler_kernel(Launch P) { step_kernel_body<true>(P); }   // MODE_STEP only
 
 // ------------------------------------------------------------------------------------------ split pipeline (MODE_STEP)
 // At 4 096 envs the monolithic launch lasts as long as its heaviest env (18 M cycles against a 4.1 M mean, 70 % of it MPR pairs run
@@ -169,7 +178,8 @@ extern "C" __global__ void __launch_bounds__(64, 2) g1_step_kernel(Launch P) {
 //                   factorisation, smooth dynamics, broadphase]; the survivors' staged geoms go to the pair queue
 //   g1_pair_kernel  (persistent waves pulling tickets, support-query pairs first): narrowphase of ONE pair per ticket, four waves
 //                   per SIMD (its own register budget and 1.8 KB of LDS) instead of two
-// so a step is 6 env launches + 5 pair launches (4 RK stages + the evaluation at the reset state of envs that ended).  Between
+// so an RK4 step is 6 env launches + 5 pair launches (4 RK stages + the evaluation at the reset state of envs that ended) and an
+// Euler step (g1_env_euler_kernel) 3 + 2 (the evaluation + the one at the reset state).  Between
 // launches an env keeps the non-union head of its LDS working set and its StepCtx in an HBM slot (14.3 KB each way: ~0.12 ms per
 // step at 4 096 envs).  Arithmetic and order of operations are those of the monolithic kernel: trajectories are bit-identical
 // (tests/test_g1_gpu.py); only the separating-direction cache differs (one entry per (env, pair); result-neutral either way).
@@ -285,7 +295,8 @@ __device__ __forceinline__ int gather_contacts(const Dev &T, const Launch &P, co
   return ncon;
 }
 
-extern "C" __global__ void __launch_bounds__(64, 2) g1_env_kernel(Launch P) {
+template <bool EULER>
+__device__ __forceinline__ void env_kernel_body(const Launch &P) {
   const int lane = threadIdx.x;
   if ((int)blockIdx.x >= P.nslots) return;
   const int env = P.order ? P.order[blockIdx.x] : (int)blockIdx.x;
@@ -318,15 +329,17 @@ extern "C" __global__ void __launch_bounds__(64, 2) g1_env_kernel(Launch P) {
     // only the per-evaluation fixed part and rows x sweeps count — a row step costs about twice as much beyond 128 rows (A from L2)
     X.work = (X.work >> 1) + 16000 + S.info[1] * (24 + (S.info[1] > 128 ? 14 : 6) * S.info[3]);   // (later evaluations weigh more: as dm_kernels.hip)
     bool again = false;
-    if (!X.after_reset) again = rk_advance(P, T, env, lane, X);
+    if (!X.after_reset) again = EULER ? euler_advance(P, T, env, lane, X) : rk_advance(P, T, env, lane, X);
     if (!again && !task_and_finish(P, T, env, lane, X)) { PROF(14); G1_PROF_OUT(); step_write_back(P, env, lane, X); if (lane == 0) wctx[WC_FINISHED] = 1; return; }
     PROF(14);
   }
-  forward_pre(T, lane, !X.after_reset && X.stage > 0);              // first half of the next evaluation
+  forward_pre<EULER>(P, T, env, lane, !X.after_reset && X.stage > 0);     // first half of the next evaluation
   emit_pairs(T, P, env, lane);
   PROF(4);                     // split pipeline: 3 = broadphase (inside), 4 = tickets + staged geoms
   ws_save(ws, X, lane);
 }
+extern "C" __global__ void __launch_bounds__(64, 2) g1_env_kernel(Launch P) { env_kernel_body<false>(P); }
+extern "C" __global__ void __launch_bounds__(64, 2) g1_env_euler_kernel(Launch P) { env_kernel_body<true>(P); }
 
 // Narrowphase of the split pipeline: persistent one-wave workgroups pull tickets (support-query pairs first: they cost ~10 x an
 // analytic pair) until the queue is empty; one ticket = one (env, pair): its staged geoms in, its contacts out.
@@ -425,6 +438,8 @@ struct DmG1Engine {
   double *dMesh = nullptr, *dClus = nullptr;
   int32_t *dOidx = nullptr;
   float *dState = nullptr, *dJT = nullptr, *dBT = nullptr, *dAR = nullptr, *dRowsE = nullptr, *dSepc = nullptr;
+  int integrator = DM_INT_RK4;   // DM_INT_*: DmG1Config.integrator, or the model's under DM_CFG_INT_MODEL
+  float *dQM = nullptr;          // Euler only: Launch::qm
   int32_t *dOrder = nullptr, *dCost = nullptr;
   float *dRows[DMG1_MAX_CLIPS] = {}, *dReset[DMG1_MAX_CLIPS] = {}, *dCom[DMG1_MAX_CLIPS] = {}, *dDebug = nullptr;
   int L[DMG1_MAX_CLIPS] = {}, flags[DMG1_MAX_CLIPS] = {};
@@ -444,6 +459,14 @@ static int g1_fail(DmG1Engine *e, int code, const char *msg) {
   if (e) e->err = msg;
   return code;
 }
+// why the last dmg1_create failed: there is no handle to carry the text, so dmg1_last_error(NULL) returns it
+static std::string g1_create_err = "null handle";
+static int g1_create_fail(DmG1Engine *e, int code, const char *msg) {
+  g1_create_err = msg;
+  fprintf(stderr, "dmg1_create: %s\n", msg);
+  delete e;
+  return code;
+}
 
 extern "C" void dmg1_default_config(DmG1Config *c) {
   memset(c, 0, sizeof *c);
@@ -451,6 +474,7 @@ extern "C" void dmg1_default_config(DmG1Config *c) {
   c->seed = 0; c->auto_reset = 1; c->device = 0;
   c->task = 0; c->amnesty_steps = 150; c->to_getup_len = 180;
   c->pipeline = 0;
+  c->integrator = DM_CFG_INT_MODEL;   // the XML's (RK4, xml :7)
 }
 extern "C" size_t dmg1_model_sizeof(void) { return sizeof(DmModelG1); }
 
@@ -643,7 +667,7 @@ static int g1_check_model(DmG1Engine *e, const DmModelG1 &m) {
   using namespace g1;
   if (m.nq != NQ || m.nv != NV || m.nu != NU || m.nbody != NB || m.ngeom != NG || m.njnt != NJ || m.nM != NM)
     return g1_fail(e, DM_EINVAL, "model dimensions are not the Unitree G1's");
-  if (m.integrator != DM_INT_RK4) return g1_fail(e, DM_EINVAL, "the G1 engine integrates with RK4 (xml :7)");
+  if (m.integrator != DM_INT_RK4 && m.integrator != DM_INT_EULER) return g1_fail(e, DM_EINVAL, "integrator must be RK4 or Euler");
   if (m.npair < 0 || m.npair > 1024) return g1_fail(e, DM_EINVAL, "npair out of range");
   if (m.jnt_type[0] != DM_JNT_FREE || m.jnt_body[0] != 1) return g1_fail(e, DM_EINVAL, "joint 0 must be the free root");
   for (int b = 2; b < NB; b++)
@@ -685,7 +709,10 @@ extern "C" int dmg1_create(const void *model, size_t model_bytes, const DmG1Conf
   e->cfg = *cfg;
   e->N = cfg->num_envs;
   int rc = g1_check_model(e, m);
-  if (rc != DM_OK) { fprintf(stderr, "dmg1_create: %s\n", e->err.c_str()); delete e; return rc; }
+  if (rc != DM_OK) { const std::string why = e->err; return g1_create_fail(e, rc, why.c_str()); }
+  if (cfg->integrator != DM_CFG_INT_MODEL && cfg->integrator != DM_CFG_INT_EULER && cfg->integrator != DM_CFG_INT_RK4)
+    return g1_create_fail(e, DM_EINVAL, "DmG1Config.integrator must be DM_CFG_INT_MODEL, DM_CFG_INT_EULER or DM_CFG_INT_RK4");
+  e->integrator = cfg->integrator == DM_CFG_INT_EULER ? DM_INT_EULER : cfg->integrator == DM_CFG_INT_RK4 ? DM_INT_RK4 : m.integrator;
   if (hipSetDevice(cfg->device) != hipSuccess) { delete e; return DM_ENODEV; }
   g1::Dev *T = new g1::Dev();
   g1_build_tables(m, *T);
@@ -715,6 +742,7 @@ extern "C" int dmg1_create(const void *model, size_t model_bytes, const DmG1Conf
   if (ok) hipMemset(e->dSepc, 0xFF, N * (4 * g1::SEPC + 4) * sizeof(float));   // pair id -1 everywhere
   ok = ok && hipMalloc(&e->dOrder, N * sizeof(int32_t)) == hipSuccess && hipMalloc(&e->dCost, N * sizeof(int32_t)) == hipSuccess;
   if (ok) hipMemset(e->dCost, 0, N * sizeof(int32_t));
+  if (e->integrator == DM_INT_EULER) ok = ok && hipMalloc(&e->dQM, N * g1::QM_STRIDE * sizeof(float)) == hipSuccess;
   e->split = cfg->pipeline == 2 || (cfg->pipeline == 0 && e->N >= 512);
 #ifdef G1_PROFILE
   if (const char *pl = getenv("DMG1_PIPELINE")) e->split = atoi(pl) == 2;
@@ -742,6 +770,7 @@ extern "C" int dmg1_create(const void *model, size_t model_bytes, const DmG1Conf
 extern "C" int dmg1_destroy(DmG1Handle e) {
   if (!e) return DM_EINVAL;
   hipFree(e->dWs); hipFree(e->dPqGeo); hipFree(e->dPqPair); hipFree(e->dPqCnt); hipFree(e->dPqCon); hipFree(e->dTick); hipFree(e->dQctr); hipFree(e->dSepc2);
+  hipFree(e->dQM);
   hipFree(e->dT); hipFree(e->dMesh); hipFree(e->dOidx); hipFree(e->dClus); hipFree(e->dState); hipFree(e->dJT); hipFree(e->dBT); hipFree(e->dAR); hipFree(e->dRowsE); hipFree(e->dSepc); hipFree(e->dOrder); hipFree(e->dCost);
   for (int c = 0; c < DMG1_MAX_CLIPS; c++) { hipFree(e->dRows[c]); hipFree(e->dReset[c]); hipFree(e->dCom[c]); }
   if (e->ev0) hipEventDestroy(e->ev0);
@@ -749,7 +778,7 @@ extern "C" int dmg1_destroy(DmG1Handle e) {
   delete e;
   return DM_OK;
 }
-extern "C" const char *dmg1_last_error(DmG1Handle e) { return e ? e->err.c_str() : "null handle"; }
+extern "C" const char *dmg1_last_error(DmG1Handle e) { return e ? e->err.c_str() : g1_create_err.c_str(); }
 
 extern "C" int dmg1_load_clip(DmG1Handle e, int clip_id, int L, const double *q, const double *v, const double *bx, const double *gx, int flags) {
   using namespace g1;
@@ -799,6 +828,8 @@ static int g1_launch(DmG1Engine *e, g1::Launch &P, void *stream, bool time_it, c
   P.N = e->N; P.nslots = nl; P.auto_reset = slots ? 0 : e->cfg.auto_reset; P.max_ep_length = e->cfg.max_ep_length;
   P.vel_obs_scale = e->cfg.vel_obs_scale; P.high_z = e->cfg.high_z; P.obs_bound = e->cfg.obs_bound; P.seed = e->cfg.seed;
   P.debug = e->dDebug;
+  P.qm = e->dQM;
+  const bool euler = P.mode == g1::MODE_STEP && e->integrator == DM_INT_EULER;   // the other modes run one evaluation and integrate nothing
   if (!e->L[0]) return g1_fail(e, DM_EINVAL, "no clip loaded (dmg1_load_clip clip 0 first)");
   if (e->cfg.task && (e->L[1] < 1 || e->L[2] < 2)) return g1_fail(e, DM_EINVAL, "combined task needs clips 0, 1, 2 = walk, run, getup");
   if (hipSetDevice(e->cfg.device) != hipSuccess) return g1_fail(e, DM_EHIP, "hipSetDevice failed");
@@ -819,7 +850,8 @@ static int g1_launch(DmG1Engine *e, g1::Launch &P, void *stream, bool time_it, c
   }
   if (P.mode == g1::MODE_STEP) P.cost = e->dCost;
   if (P.mode == g1::MODE_STEP && e->split) {
-    // split pipeline: 6 env launches around 5 pair launches (4 RK stages + the evaluation at the reset state of envs that ended)
+    // split pipeline: 6 env launches around 5 pair launches (4 RK stages + the evaluation at the reset state of envs that ended);
+    // under Euler 3 around 2.  The counters of the rounds that do not run stay at the zeros of the memset (dmg1_queue_counters).
     P.ws = e->dWs; P.pq_geo = e->dPqGeo; P.pq_pair = e->dPqPair; P.pq_cnt = e->dPqCnt; P.pq_con = e->dPqCon; P.tick = e->dTick;
     P.qctr = e->dQctr; P.sepc2 = e->dSepc2;
     hipMemsetAsync(e->dQctr, 0, 8 * 4 * sizeof(int32_t), s);
@@ -828,14 +860,18 @@ static int g1_launch(DmG1Engine *e, g1::Launch &P, void *stream, bool time_it, c
     Q.T = e->dT; Q.mesh_vert = e->dMesh; Q.mesh_oidx = e->dOidx; Q.mesh_clus = e->dClus; Q.pq_geo = e->dPqGeo; Q.pq_pair = e->dPqPair;
     Q.pq_cnt = e->dPqCnt; Q.pq_con = e->dPqCon; Q.tick = e->dTick; Q.sepc2 = e->dSepc2; Q.N = e->N;
     const int pair_waves = std::min(nl * 8, 256 * 4 * G1_PAIR_WAVES);   // persistent: every wave pulls tickets until the queue is empty
-    for (int r = 0; r < 6; r++) {
+    const int rounds = euler ? 3 : 6;
+    for (int r = 0; r < rounds; r++) {
       P.round = r;
-      hipLaunchKernelGGL(g1::g1_env_kernel, dim3(nl), dim3(64), 0, s, P);
-      if (r < 5) {
+      if (euler) hipLaunchKernelGGL(g1::g1_env_euler_kernel, dim3(nl), dim3(64), 0, s, P);
+      else hipLaunchKernelGGL(g1::g1_env_kernel, dim3(nl), dim3(64), 0, s, P);
+      if (r < rounds - 1) {
         Q.qctr = e->dQctr + 4 * r;
         hipLaunchKernelGGL(g1::g1_pair_kernel, dim3(pair_waves), dim3(64), 0, s, Q);
       }
     }
+  } else if (euler) {
+    hipLaunchKernelGGL(g1::g1_step_euler_kernel, dim3(nl), dim3(64), 0, s, P);
   } else {
     hipLaunchKernelGGL(g1::g1_step_kernel, dim3(nl), dim3(64), 0, s, P);
   }

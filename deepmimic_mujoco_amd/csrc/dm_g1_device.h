@@ -16,6 +16,7 @@ namespace g1 {
 constexpr int NQ = 44, NV = 43, NU = 37, NB = 39, NG = 94, NJ = 38, NM = 434, NACT = 23, NOBS = 85, NREW = 23;
 constexpr int MAXCON = DMG1_MAXCON, MAXROW = DMG1_MAXROW, MAXANC = 16, MAXSURV = 384, NCG = 48;   // NCG: geoms that collide (47)
 constexpr int PAIRCAP = 128;    // split pipeline: surviving pairs per env and evaluation that the pair queue holds (monolithic: MAXSURV)
+constexpr int QM_STRIDE = 448;  // Euler: floats per env of the parked mass matrix (NM entries, rows of 64 B)
 constexpr int STATE = 176;   // floats per env in the HBM state row
 constexpr int S_QPOS = 0, S_QVEL = 44, S_WARM = 87, S_CTRL = 130, S_IDX = 167, S_EPLEN = 168, S_EPREW = 169, S_RCNT = 170, S_MOTION = 171;
 constexpr int NOBS_C = DMG1_NOBS_COMBINED;   // DPCombinedEnv: 82 + extra contacts 8 + phase + player-action obs 7
@@ -156,6 +157,7 @@ struct Launch {
   int32_t *qctr;             // per round: tickets in list 0, in list 1, queue head, pad
   float *sepc2;              // [N][1024][4]: separating-direction cache, one entry per (env, pair)
   int32_t round, pad3;
+  float *qm;                 // Euler kernels: [N][QM_STRIDE], the unfactored M of the evaluation (park_m -> euler_damped_qacc); else null
 };
 
 struct PairLaunch {

@@ -1,5 +1,5 @@
 // dm_g1_dynamics.h — position and velocity stage of one forward evaluation: pose chain, centre of mass, composite inertia and
-// L^T D L factorisation, the solves with it, smooth dynamics, and the position integrator.
+// L^T D L factorisation, the solves with it, smooth dynamics, the position integrator, and the damped solve of the Euler integrator.
 #pragma once
 #include "dm_g1_device.h"
 #include "dm_g1_math.h"
@@ -147,6 +147,35 @@ struct RowSolve {
   }
 };
 
+// The entries of M (armature included) of the lane's dof, from the composite inertia in S.u.sm.crb: put(index in qM, value)
+template <class Put>
+__device__ __forceinline__ void m_entries(const Dev &T, const int lane, Put put) {
+  if (lane < NV) {
+    const int i = lane;
+    float buf[6], cd[6];
+    for (int q = 0; q < 6; q++) cd[q] = S.cdof[i][q];
+    mul_inert_vec(buf, S.u.sm.crb[T.d_body[i]], cd);
+    int adr = T.d_madr[i];
+    float v = T.d_arm[i];
+    for (int q = 0; q < 6; q++) v += cd[q] * buf[q];
+    put(adr, v);
+    const int n = T.d_nanc[i];
+    const uint4 aw = *reinterpret_cast<const uint4 *>(T.d_anc[i]);   // the whole ancestor list in one load (a loop over T.d_anc[i][a]
+    const uint32_t awv[4] = {aw.x, aw.y, aw.z, aw.w};                  // waits for one global load per ancestor)
+#pragma unroll
+    for (int a = 0; a < 14; a++) {
+      if (a < n) {
+        const int j = (awv[a >> 2] >> (8 * (a & 3))) & 255;
+        float s = 0;
+        for (int q = 0; q < 6; q++) s += S.cdof[j][q] * buf[q];
+        put(adr + 1 + a, s);
+      }
+    }
+  }
+}
+
+__device__ __forceinline__ void factor_ldl(const Dev &T, const int lane);
+
 __device__ __noinline__ void crb_factor(const Dev &T, const int lane) {   // [EXT] mj_crb + mj_factorM
   if (lane < NB) {
     float acc[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -160,29 +189,21 @@ __device__ __noinline__ void crb_factor(const Dev &T, const int lane) {   // [EX
     for (int i = 0; i < 10; i++) S.u.sm.crb[lane][i] = acc[i];
   }
   SYNC();
-  if (lane < NV) {
-    const int i = lane;
-    float buf[6], cd[6];
-    for (int q = 0; q < 6; q++) cd[q] = S.cdof[i][q];
-    mul_inert_vec(buf, S.u.sm.crb[T.d_body[i]], cd);
-    int adr = T.d_madr[i];
-    float v = T.d_arm[i];
-    for (int q = 0; q < 6; q++) v += cd[q] * buf[q];
-    S.qLD[adr] = v;
-    const int n = T.d_nanc[i];
-    const uint4 aw = *reinterpret_cast<const uint4 *>(T.d_anc[i]);   // the whole ancestor list in one load (a loop over T.d_anc[i][a]
-    const uint32_t awv[4] = {aw.x, aw.y, aw.z, aw.w};                  // waits for one global load per ancestor)
-#pragma unroll
-    for (int a = 0; a < 14; a++) {
-      if (a < n) {
-        const int j = (awv[a >> 2] >> (8 * (a & 3))) & 255;
-        float s = 0;
-        for (int q = 0; q < 6; q++) s += S.cdof[j][q] * buf[q];
-        S.qLD[adr + 1 + a] = s;
-      }
-    }
-  }
+  m_entries(T, lane, [&](const int i, const float v) { S.qLD[i] = v; });
   SYNC();
+  factor_ldl(T, lane);
+}
+
+// Euler integrator only: the unfactored M of this evaluation into the env's row of Launch::qm, between crb_factor and fwd_smooth,
+// while S.u.sm.crb still holds the composite inertia.  The collision stage overwrites that part of the LDS union, so the second
+// factorisation of the step (euler_damped_qacc, after PGS) takes its M from here.
+__device__ __noinline__ void park_m(const Launch &P, const Dev &T, const int env, const int lane) {
+  float *qm = P.qm + (size_t)env * QM_STRIDE;
+  m_entries(T, lane, [&](const int i, const float v) { qm[i] = v; });
+}
+
+// In-place elimination of the M entries in S.qLD, and the reciprocals of its diagonal
+__device__ __forceinline__ void factor_ldl(const Dev &T, const int lane) {
   // L^T D L, rows of dof k: [k, parent(k), grand-parent, ...]; step k updates the rows of its ancestors.  The dof tree is
   // compile-time (dm_g1_topology.h): per step the only run-time table is the target entry of the lane's ancestor pair, and
   // those (43 steps x up to 105 pairs) are requested in one batch before the first step — a loop over T.d_anc / T.d_madr was
@@ -353,6 +374,23 @@ __device__ void integrate_pos(const Dev &T, const float *vel, const double a, co
     S.qpos[lane + 1] = hi;
     if (lo) S.u.rk.qlo[lane + 1] = l;
   }
+}
+
+// [EXT] mj_Euler's implicit joint damping, after the evaluation: S.tmp <- qacc' with (M + h B) qacc' = qfrc_smooth + qfrc_constraint,
+// B = diag(damping), computed as qacc' = qacc - (M + h B)^-1 h B qacc (the correction is small against qacc: fp32 keeps more of it
+// than a solve of the summed forces would).  M: the entries park_m kept; the factor in S.qLD, S.dinv, S.dsq is that of M + h B
+// afterwards — nothing reads them before the next evaluation's crb_factor.  S.qacc is left as the evaluation wrote it.
+__device__ __noinline__ void euler_damped_qacc(const Dev &T, const float *qm, const int lane) {
+  for (int i = lane; i < NM; i += 64) S.qLD[i] = qm[i];
+  float hb = 0;
+  if (lane < NV) { hb = T.timestep * T.d_damp[lane]; S.tmp[lane] = hb * S.qacc[lane]; }
+  SYNC();
+  if (lane < NV) S.qLD[T.d_madr[lane]] += hb;
+  SYNC();
+  factor_ldl(T, lane);
+  solve_m(T, S.tmp, lane);
+  if (lane < NV) S.tmp[lane] = S.qacc[lane] - S.tmp[lane];
+  SYNC();
 }
 
 }  // namespace g1

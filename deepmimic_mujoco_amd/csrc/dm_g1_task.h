@@ -1,4 +1,4 @@
-// dm_g1_task.h — what a step does around its forward evaluations: entry by launch mode, RK4 bookkeeping, the task layer of
+// dm_g1_task.h — what a step does around its forward evaluations: entry by launch mode, RK4 / Euler bookkeeping, the task layer of
 // DPEnv(robot="unitree_g1") and DPCombinedEnv with the in-kernel auto-reset, and the write-back of the state row.
 #pragma once
 #include "dm_g1_device.h"
@@ -140,6 +140,36 @@ __device__ __forceinline__ bool rk_advance(const Launch &P, const Dev &T, const 
     integrate_pos(T, S.accq, 1.0, false, lane);
     SYNC();
   }
+  return false;
+}
+
+// MODE_STEP under DM_INT_EULER, after the step's one evaluation ([EXT] mj_step with mj_Euler): the bookkeeping of RK stage 0, then
+// qvel += h qacc' with the joint damping implicit (euler_damped_qacc) and qpos integrated with the NEW qvel.  S.qacc and S.warm stay
+// the evaluation's (MuJoCo's warm start is forward's qacc, not qacc'); the derived arrays the task layer reads are those of the
+// pre-step pose.  Only the Euler kernels (template argument of the kernel bodies, dm_g1.hip) call it.  euler_integrate is out of
+// line and does not take the StepCtx (whose address must not escape: it lives in registers); it returns mj_checkAcc's verdict.
+__device__ __noinline__ bool euler_integrate(const Launch &P, const Dev &T, const int env, const int lane) {
+  if (P.debug) {   // the contact hash of rk_advance, before anything reuses the contact arrays; the RK stages that do not exist read 0
+    unsigned hsh = 0;
+    for (int c = 0; c < S.info[0]; c++) hsh = (hsh * 131u + (unsigned)S.u.co.c_g1[c] * 97u + (unsigned)S.u.co.c_g2[c] + 1u) & 0xFFFFFFu;
+    if (lane < 4) P.debug[(size_t)env * DMG1_DEBUG_STRIDE + DMG1_DBG_STAGE_CHASH + lane] = (lane == 0) ? (float)hsh : 0.f;
+  }
+  const bool badv = (lane < NV) && !(fabsf(S.qacc[lane]) <= MAXVALF);   // mj_checkAcc
+  const bool sim_err = __any(badv);
+  if (!sim_err) {
+    if (lane < NQ) S.x0q[lane] = S.qpos[lane];
+    euler_damped_qacc(T, P.qm + (size_t)env * QM_STRIDE, lane);
+    if (lane < NV) S.qvel[lane] += T.timestep * S.tmp[lane];
+    SYNC();
+    integrate_pos(T, S.qvel, 1.0, false, lane);
+    SYNC();
+  }
+  return sim_err;
+}
+// The stage-0 bookkeeping of rk_advance, then the step's final state.  Always false: no further evaluation.
+__device__ __forceinline__ bool euler_advance(const Launch &P, const Dev &T, const int env, const int lane, StepCtx &X) {
+  X.stage_ncon |= (unsigned)S.info[0] & 0xFF; X.stage_nefc_lo |= (unsigned)S.info[1] & 0xFF;
+  X.sim_err = euler_integrate(P, T, env, lane);
   return false;
 }
 

@@ -157,18 +157,20 @@ class HipDeepMimicVecEnv(HipBatchEnv):
     """N DPEnv instances as one HIP batch with SubprocVecEnv semantics (auto-reset, terminal_observation).
 
     ``motion`` may be one clip name or a list (per-env clip id = env index mod len(list): BASELINE
-    config 5).  ``step_tensor`` is the zero-copy path used by deepmimic_mujoco_amd.ppo.
+    config 5).  ``step_tensor`` is the zero-copy path used by deepmimic_mujoco_amd.ppo.  ``integrator`` (None / "model", "RK4",
+    "Euler") goes to whichever engine the robot has.
     """
 
     version, ENV_CFG = DPEnv.version, DPEnv.ENV_CFG
 
-    def __new__(cls, num_envs, motion=None, robot="humanoid3d", device=0, seed=1234, auto_reset=True, sub_batches=1):
+    def __new__(cls, num_envs, motion=None, robot="humanoid3d", device=0, seed=1234, auto_reset=True, sub_batches=1, integrator=None):
         if robot == "unitree_g1" and cls is HipDeepMimicVecEnv:
             from .g1 import HipG1VecEnv
-            return HipG1VecEnv(num_envs, motion=motion, device=device, seed=seed, auto_reset=auto_reset, sub_batches=sub_batches)
+            return HipG1VecEnv(num_envs, motion=motion, device=device, seed=seed, auto_reset=auto_reset, sub_batches=sub_batches,
+                               integrator=integrator)
         return super().__new__(cls)
 
-    def __init__(self, num_envs, motion=None, robot="humanoid3d", device=0, seed=1234, auto_reset=True, sub_batches=1):
+    def __init__(self, num_envs, motion=None, robot="humanoid3d", device=0, seed=1234, auto_reset=True, sub_batches=1, integrator=None):
         import torch
         self.robot_config = RobotConfig(robot)
         model = load_model(self.robot_config.xml_path)
@@ -181,7 +183,8 @@ class HipDeepMimicVecEnv(HipBatchEnv):
             self.mocaps.append(mc)
 
         def make(nk, k):
-            e = _lib.HipEngine(model, nk, device=device, seed=seed + 104729 * k, auto_reset=auto_reset, low_z=self.robot_config.low_z)
+            e = _lib.HipEngine(model, nk, device=device, seed=seed + 104729 * k, auto_reset=auto_reset, low_z=self.robot_config.low_z,
+                               integrator=integrator)
             for cid, (m, mc) in enumerate(zip(self.motions, self.mocaps)):
                 mcfg = MotionConfig(m, robot)
                 e.load_clip(cid, mc, floor=m in mcfg.floor_motions, acyclic=m in mcfg.acyclical_motions)

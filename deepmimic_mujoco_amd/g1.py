@@ -13,7 +13,7 @@ import os
 import numpy as np
 
 from . import mjcf, model as _model
-from ._lib import EngineBase, load_library
+from ._lib import INTEGRATORS, EngineBase, load_library
 from .vec_env import Box, HipBatchEnv, HipImitationEnv, HipSingleEnv, _LazyCombinedInfos, _action_space, _combined_info
 from .config import RobotConfig
 
@@ -140,7 +140,8 @@ def load_g1_model():
 class DmG1Config(C.Structure):
     _fields_ = [("num_envs", C.c_int32), ("max_ep_length", C.c_int32), ("vel_obs_scale", C.c_float), ("high_z", C.c_float),
                 ("obs_bound", C.c_float), ("seed", C.c_uint64), ("auto_reset", C.c_int32), ("device", C.c_int32),
-                ("task", C.c_int32), ("amnesty_steps", C.c_int32), ("to_getup_len", C.c_int32), ("pipeline", C.c_int32)]
+                ("task", C.c_int32), ("amnesty_steps", C.c_int32), ("to_getup_len", C.c_int32), ("pipeline", C.c_int32),
+                ("integrator", C.c_int32)]
 
 
 _BOUND = []
@@ -189,13 +190,19 @@ class G1HipEngine(EngineBase):
 
     PREFIX, DEBUG_STRIDE, NQ, NV, NBODY = "dmg1_", DEBUG_STRIDE, NQ, NV, NBODY
 
-    def __init__(self, num_envs, device=0, seed=0, auto_reset=True, max_ep_length=1000, task=TASK_DPENV, pipeline=0):
+    def __init__(self, num_envs, device=0, seed=0, auto_reset=True, max_ep_length=1000, task=TASK_DPENV, pipeline=0, integrator=None,
+                 cmodel=None):
+        """``integrator``: None / "model" (the model's: RK4 in the XML), "RK4" or "Euler" (MuJoCo's semi-implicit Euler with implicit
+        joint damping: one forward evaluation per step instead of four), as :class:`_lib.HipEngine`.  ``cmodel``: a
+        :class:`DmModelG1` to create the engine from instead of the packaged model's (an edited copy of it)."""
         import torch
         if not torch.cuda.is_available():
             raise RuntimeError("G1HipEngine needs an MI355X (torch.cuda.is_available() is False); there is no CPU fallback")
         self.torch = torch
         self.L = _lib()
         self.gmodel, self.cmodel = load_g1_model()
+        if cmodel is not None:
+            self.cmodel = cmodel
         self.N = int(num_envs)
         self.device = torch.device("cuda", device)
         cfg = DmG1Config()
@@ -203,6 +210,7 @@ class G1HipEngine(EngineBase):
         cfg.num_envs, cfg.seed, cfg.auto_reset, cfg.device, cfg.max_ep_length = self.N, seed, int(auto_reset), device, max_ep_length
         cfg.task = int(task)
         cfg.pipeline = int(pipeline)        # 0 auto (split pipeline from 512 envs up), 1 monolithic, 2 split
+        cfg.integrator = INTEGRATORS[integrator]
         self.auto_reset = bool(auto_reset)
         self.split = int(pipeline) == 2 or (int(pipeline) == 0 and self.N >= 512)      # the rule of dmg1_create (csrc/dm_g1.hip)
         self.task = int(task)
@@ -211,7 +219,7 @@ class G1HipEngine(EngineBase):
         self.h = C.c_void_p()
         rc = self.L.dmg1_create(C.byref(self.cmodel), C.sizeof(DmModelG1), C.byref(cfg), C.byref(self.h))
         if rc != 0:
-            raise RuntimeError("dmg1_create failed: %d" % rc)
+            raise RuntimeError("dmg1_create failed (%d): %s" % (rc, (self.L.dmg1_last_error(None) or b"").decode()))
         self.clip_len = 0
         self._debug = None
 
@@ -311,7 +319,7 @@ class HipG1VecEnv(HipBatchEnv):
     when asked for ``robot="unitree_g1"``.  Actions are the policy's 23 values (src/deepmimic_env.py:303-307).
     ``motion`` may be a list (per-env clip id = env index mod len(list), as BASELINE config 5 mixes clips)."""
 
-    def __init__(self, num_envs, motion=None, device=0, seed=1234, auto_reset=True, sub_batches=1):
+    def __init__(self, num_envs, motion=None, device=0, seed=1234, auto_reset=True, sub_batches=1, integrator=None):
         from .deepmimic_env import DPEnvConfig
         motions = [motion] if (motion is None or isinstance(motion, str)) else list(motion)
         assert 1 <= len(motions) <= 8, "an engine holds up to 8 clips (DMG1_MAX_CLIPS)"
@@ -322,7 +330,8 @@ class HipG1VecEnv(HipBatchEnv):
         self.robot_config = RobotConfig("unitree_g1")
 
         def make(nk, k):
-            e = G1HipEngine(nk, device=device, seed=seed + 104729 * k, auto_reset=auto_reset, max_ep_length=DPEnvConfig().MAX_EP_LENGTH)
+            e = G1HipEngine(nk, device=device, seed=seed + 104729 * k, auto_reset=auto_reset, max_ep_length=DPEnvConfig().MAX_EP_LENGTH,
+                            integrator=integrator)
             for cid, (mcfg, mc) in enumerate(pairs):
                 _load(e, mcfg, mc, clip_id=cid)
             if len(pairs) > 1:
@@ -355,7 +364,7 @@ class G1DPEnv(HipImitationEnv):
     version = "v1.0"
     REASONS = REASONS      # the G1 table has reason 8, the run clip's roll / pitch limit
 
-    def __init__(self, motion=None, load_mocap=True, robot="unitree_g1", _profile=False, device=0):
+    def __init__(self, motion=None, load_mocap=True, robot="unitree_g1", _profile=False, device=0, integrator=None):
         import random
         import torch
         from .deepmimic_env import DPEnvConfig
@@ -368,7 +377,7 @@ class G1DPEnv(HipImitationEnv):
         self.ENV_CFG = DPEnvConfig()
         self.robot_config = RobotConfig("unitree_g1")
         self.motion_config, self.mocap = _g1_mocap(motion)
-        self._eng = G1HipEngine(1, device=device, auto_reset=False, max_ep_length=self.ENV_CFG.MAX_EP_LENGTH)
+        self._eng = G1HipEngine(1, device=device, auto_reset=False, max_ep_length=self.ENV_CFG.MAX_EP_LENGTH, integrator=integrator)
         _load(self._eng, self.motion_config, self.mocap)
         self.model = self._eng.gmodel
         self._out = self._eng.alloc_outputs()
@@ -395,10 +404,11 @@ COMBINED_CLIPS = ("walk", "run", "getup_facedown_towalk")      # src/combined_en
 MOTION_WALK, MOTION_RUN, MOTION_GETUP, MOTION_TO_GETUP = 0, 1, 2, 3
 
 
-def _combined_engine(num_envs, device, seed, auto_reset):
+def _combined_engine(num_envs, device, seed, auto_reset, integrator=None):
     from .combined_env import DPCombinedEnvConfig
     cfg = DPCombinedEnvConfig()
-    eng = G1HipEngine(num_envs, device=device, seed=seed, auto_reset=auto_reset, max_ep_length=cfg.MAX_EP_LENGTH, task=TASK_COMBINED)
+    eng = G1HipEngine(num_envs, device=device, seed=seed, auto_reset=auto_reset, max_ep_length=cfg.MAX_EP_LENGTH, task=TASK_COMBINED,
+                      integrator=integrator)
     mocaps = []
     for cid, m in enumerate(COMBINED_CLIPS):
         mcfg, mc = _g1_mocap(m)
@@ -411,12 +421,12 @@ class HipG1CombinedVecEnv(HipG1VecEnv):
     """N ``DPCombinedEnv()`` instances — the reference's training environment (src/sb3_ppo.py:277-278): Unitree G1, walk / run /
     getup / to_getup motion state machine, obs 98, 23 actions — as one HIP batch with SubprocVecEnv semantics."""
 
-    def __init__(self, num_envs, device=0, seed=1234, auto_reset=True, sub_batches=1):
+    def __init__(self, num_envs, device=0, seed=1234, auto_reset=True, sub_batches=1, integrator=None):
         self.mocaps = None
         self.robot_config = RobotConfig("unitree_g1")
 
         def make(nk, k):
-            e, mocaps = _combined_engine(nk, device, seed + 104729 * k, auto_reset)
+            e, mocaps = _combined_engine(nk, device, seed + 104729 * k, auto_reset, integrator)
             self.mocaps = self.mocaps or mocaps
             return e
         # action space = ctrlrange / ACT_SCALE (src/combined_env.py:196-200)
@@ -431,7 +441,7 @@ class G1CombinedEnv(HipSingleEnv):
 
     version = "v0.2.up"
 
-    def __init__(self, verbose=0, _profile=False, device=0):
+    def __init__(self, verbose=0, _profile=False, device=0, integrator=None):
         import random
         import torch
         from .combined_env import DPCombinedEnvConfig, MTToGetup, PAWalk
@@ -439,7 +449,7 @@ class G1CombinedEnv(HipSingleEnv):
         self.ENV_CFG = DPCombinedEnvConfig()
         self.robot = "unitree_g1"
         self.robot_config = RobotConfig(self.robot)
-        self._eng, mocaps = _combined_engine(1, device, 0, False)
+        self._eng, mocaps = _combined_engine(1, device, 0, False, integrator)
         self.walk_mocap, self.run_mocap, self.getup_mocap = mocaps
         self.action_mocap = None
         self.to_getup_mocap = MTToGetup(self.getup_mocap)

@@ -27,6 +27,9 @@ def build_parser():
                     help="env_name of src/sb3_ppo.py:247-248 (dp_combined_env: walk/run/getup state machine on humanoid3d)")
     ap.add_argument("--robot", default="humanoid3d", choices=["humanoid3d", "unitree_g1"],
                     help="src/sb3_ppo.py:251 trains unitree_g1 (its dp_combined_env is hard-wired to it)")
+    ap.add_argument("--integrator", default="model", choices=["model", "RK4", "Euler"],
+                    help="time integration of the training env and of the --eval-envs twin, on either robot: model = the XML's (RK4); "
+                         "Euler = MuJoCo's semi-implicit Euler with implicit joint damping, one forward evaluation per step instead of four")
     ap.add_argument("--envs", type=int, default=4096)
     ap.add_argument("--horizon", type=int, default=32)          # 32 x 4096 = the reference's 4096 x 32 batch
     ap.add_argument("--epochs", type=int, default=20)           # src/sb3_ppo.py:259
@@ -65,11 +68,12 @@ def _eval_batch_env(args, motions, local_rank):
     from .deepmimic_env import HipDeepMimicVecEnv
     if args.env == "dp_combined_env":
         from .combined_env import HipCombinedVecEnv
-        return HipCombinedVecEnv(args.eval_envs, robot=args.robot, device=local_rank, seed=4321, auto_reset=False)
+        return HipCombinedVecEnv(args.eval_envs, robot=args.robot, device=local_rank, seed=4321, auto_reset=False, integrator=args.integrator)
     if args.robot == "unitree_g1":
-        return HipDeepMimicVecEnv(args.eval_envs, motion=motions[0], robot="unitree_g1", device=local_rank, seed=4321, auto_reset=False)
+        return HipDeepMimicVecEnv(args.eval_envs, motion=motions[0], robot="unitree_g1", device=local_rank, seed=4321, auto_reset=False,
+                                  integrator=args.integrator)
     return HipDeepMimicVecEnv(args.eval_envs, motion=motions if len(motions) > 1 else motions[0], device=local_rank, seed=4321,
-                              auto_reset=False)
+                              auto_reset=False, integrator=args.integrator)
 
 
 def main(argv=None):
@@ -101,13 +105,14 @@ def main(argv=None):
     sb = args.sub_batches if args.envs % args.sub_batches == 0 else 1
     if args.env == "dp_combined_env":                                   # src/sb3_ppo.py:276-278
         from .combined_env import HipCombinedVecEnv
-        env = HipCombinedVecEnv(args.envs, robot=args.robot, device=local_rank, seed=1234 + 7919 * rank,
+        env = HipCombinedVecEnv(args.envs, robot=args.robot, device=local_rank, seed=1234 + 7919 * rank, integrator=args.integrator,
                                 **({"sub_batches": sb} if args.robot == "unitree_g1" else {}))      # (the humanoid3d variant has one engine)
     elif args.robot == "unitree_g1":                                    # src/sb3_ppo.py:274-275 with robot = "unitree_g1"
-        env = HipDeepMimicVecEnv(args.envs, motion=motions[0], robot="unitree_g1", device=local_rank, seed=1234 + 7919 * rank, sub_batches=sb)
+        env = HipDeepMimicVecEnv(args.envs, motion=motions[0], robot="unitree_g1", device=local_rank, seed=1234 + 7919 * rank, sub_batches=sb,
+                                 integrator=args.integrator)
     else:
         env = HipDeepMimicVecEnv(args.envs, motion=motions if len(motions) > 1 else motions[0], device=local_rank,
-                                 seed=1234 + 7919 * rank, sub_batches=sb)
+                                 seed=1234 + 7919 * rank, sub_batches=sb, integrator=args.integrator)
     if args.algo == "sac":
         return _train_sac(args, env, motions, local_rank)
     ppo = PPO(env, net_arch=tuple(int(x) for x in args.arch.split(",")), n_steps=args.horizon,
@@ -152,7 +157,7 @@ def main(argv=None):
             roll = sum(h["rollout_s"] for h in steady) / len(steady)
             trn = sum(h["train_s"] for h in steady) / len(steady)
             per_it = args.envs * args.horizon * world
-            print(json.dumps({"workload": "ppo", "n_gpus": world, "envs_per_gpu": args.envs, "horizon": args.horizon,
+            print(json.dumps({"workload": "ppo", "integrator": args.integrator, "n_gpus": world, "envs_per_gpu": args.envs, "horizon": args.horizon,
                               "arch": args.arch, "epochs": args.epochs, "minibatch": args.minibatch,
                               "buffer_dtype": str(ppo.buffer_dtype).replace("torch.", ""), "rollout_path": ppo.rollout_path(),
                               "learner": ppo.learner_path(),
@@ -212,7 +217,7 @@ def _train_sac(args, env, motions, local_rank):
         batch_env.close()
     if args.json:
         last = hist[-1] if hist else {}
-        print(json.dumps({"workload": "sac", "envs": env.num_envs, "arch": args.arch, "buffer_size": args.buffer_size,
+        print(json.dumps({"workload": "sac", "integrator": args.integrator, "envs": env.num_envs, "arch": args.arch, "buffer_size": args.buffer_size,
                           "gradient_steps": args.gradient_steps, "total_timesteps": sac.num_timesteps, "n_updates": sac._n_updates,
                           "env_steps_per_s": sac.num_timesteps / dt, "wall_s": dt,
                           "ep_rew_mean": last.get("ep_rew_mean"), "ep_len_mean": last.get("ep_len_mean"),

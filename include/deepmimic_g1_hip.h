@@ -34,6 +34,13 @@ typedef struct DmG1Engine *DmG1Handle;
 #define DMG1_DEBUG_STRIDE 1024
 #define DMG1_MAX_CLIPS 8   /* clip slots per engine (as DM_MAX_CLIPS of deepmimic_hip.h) */
 
+/* Integrator selector (DmG1Config.integrator): the constants of deepmimic_hip.h */
+#ifndef DM_CFG_INT_MODEL
+#define DM_CFG_INT_MODEL 0
+#define DM_CFG_INT_EULER 1
+#define DM_CFG_INT_RK4 2
+#endif
+
 typedef struct DmG1Config {
   int32_t num_envs;
   int32_t max_ep_length;   /* 1000 (DPEnvConfig.MAX_EP_LENGTH) */
@@ -52,6 +59,11 @@ typedef struct DmG1Config {
   int32_t pipeline;        /* how dmg1_step runs: 0 (default) = split pipeline from 512 envs up, else monolithic; 1 = monolithic (one wave
                             * runs its env's whole step); 2 = split (per evaluation a per-env launch and a batch-wide narrowphase launch with
                             * one wave per colliding PAIR; ~135 KB of device memory per env).  Same results either way. */
+  int32_t integrator;      /* DmConfig.integrator's meaning and constants: DM_CFG_INT_MODEL (default) = <option integrator> of the
+                            * model (RK4, xml :7; a model struct with DM_INT_EULER steps with Euler); DM_CFG_INT_EULER = MuJoCo's
+                            * semi-implicit Euler with implicit joint damping [EXT mj_Euler]: one forward evaluation per step
+                            * instead of four; DM_CFG_INT_RK4.  Any other value: dmg1_create returns DM_EINVAL and
+                            * dmg1_last_error(NULL) says why. */
 } DmG1Config;
 
 void dmg1_default_config(DmG1Config *cfg);
@@ -60,6 +72,7 @@ size_t dmg1_model_sizeof(void);
 /* Replaces MujocoEnv.__init__(xml, 6) (src/deepmimic_env.py:301) for robot="unitree_g1", one instance per batch. */
 int dmg1_create(const void *model, size_t model_bytes, const DmG1Config *cfg, DmG1Handle *out);
 int dmg1_destroy(DmG1Handle h);
+/* Text of the handle's last failure; with a NULL handle, why the last dmg1_create failed ("null handle" before any did). */
 const char *dmg1_last_error(DmG1Handle h);
 
 /* Replaces DPEnv.load_mocap (src/deepmimic_env.py:321-324): HOST float64 tables of MocapDM(robot="unitree_g1"):
@@ -76,7 +89,11 @@ int dmg1_reset(DmG1Handle h, const uint8_t *mask, const int32_t *idx_init, float
 /* Replaces DPEnv.step(action) for every env (src/deepmimic_env.py:335-484) plus the VecEnv worker's auto-reset.
  * actions float[N*23] (scaled by 20 and padded with 14 zeros inside, :348-351); obs float[N*85]; rew float[N]; done uint8[N];
  * terms float[N*5]; reason int32[N] (DM_REASON_* of deepmimic_hip.h, 8 = run angle rule); terminal_obs float[N*85].
- * terms, reason, terminal_obs may be NULL. */
+ * terms, reason, terminal_obs may be NULL.
+ * Launches per step.  Monolithic pipeline: one g1_step_kernel (RK4: its wave runs 4 evaluations) or one g1_step_euler_kernel (1
+ * evaluation), + 1 evaluation at the reset state of an env that ended.  Split pipeline: RK4 6 g1_env_kernel + 5 g1_pair_kernel (4 RK
+ * stages + the evaluation at the reset state), Euler 3 g1_env_euler_kernel + 2 g1_pair_kernel (the evaluation + the one at the
+ * reset state).  From 512 envs up one g1_schedule_kernel goes in front. */
 int dmg1_step(DmG1Handle h, const float *actions, float *obs, float *rew, uint8_t *done, float *terms, int32_t *reason,
               float *terminal_obs, void *stream);
 
@@ -126,7 +143,8 @@ int dmg1_set_motion(DmG1Handle h, const int32_t *motion, void *stream);
  *  [0:117) xpos | [117:160) qacc_smooth | [160:203) qacc | 203 ncon | 204 nefc | 205 solver_iter | 206 nlimit | 207 overflow |
  *  [208:208+48*9) per contact: dist, geom1, geom2, pos3, normal3 | [640:640+256) efc_force |
  *  after a step, per RK stage k = 0..3: 1000+k contacts, 1004+k rows (low byte), 1012+k a 24-bit hash of the stage's contact
- *  list h <- (131 h + 97 geom1 + geom2 + 1) mod 2^24 (the oracle keeps the same: "stage_chash<k>") |
+ *  list h <- (131 h + 97 geom1 + geom2 + 1) mod 2^24 (the oracle keeps the same: "stage_chash<k>"); under the Euler integrator
+ *  the step has stage 0 only and the entries of k = 1..3 are written as 0 |
  *  1008 broadphase survivors, 1009 / 1010 / 1011 of them analytic, plane - mesh and MPR pairs |
  *  [900:916) per-phase clock sums of the diagnostic build (-DG1_PROFILE) */
 #define DMG1_DBG_XPOS 0
@@ -150,7 +168,8 @@ int dmg1_set_debug(DmG1Handle h, float *debug);
 
 /* Diagnostics of the split pipeline: per round r = 0..5 of the LAST dmg1_step or dmg1_step_active, whichever came last,
  * host_out[4 r + 0 / 1 / 2] = tickets of support-query pairs (MPR, plane-mesh), of analytic pairs, and tickets pulled.
- * Synchronises the device.  Zeros when monolithic. */
+ * Synchronises the device.  Zeros when monolithic, and for the rounds that did not run (an Euler step has rounds 0..2, of which
+ * 0 and 1 file tickets). */
 int dmg1_queue_counters(DmG1Handle h, int32_t *host_out24);
 
 /* Test hooks of the separating-direction cache of the MPR pairs (result-neutral by design; tests/test_g1_pair_cover_gpu.py).
