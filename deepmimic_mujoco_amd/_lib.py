@@ -35,6 +35,8 @@ EXPORTS = ["dm_default_config", "dm_create", "dm_destroy", "dm_last_error", "dm_
            "dm_rollout_finish", "dm_rollout_finish_workspace_bytes",
            "dm_policy_forward_bf16", "dm_rollout_store_bf16", "dm_ppo_gather_bf16", "dm_flat_adam_step_gather_bf16",
            "dm_step_active", "dm_eval_advance"]
+# include/deepmimic_render.h (csrc/dm_render.hip); EXPORTS above is the list of include/deepmimic_hip.h alone
+RENDER_EXPORTS = ["dm_render_create", "dm_render_destroy", "dm_render_last_error", "dm_render_kinematics", "dm_render_cast", "dm_render"]
 
 
 class DmConfig(C.Structure):
@@ -184,6 +186,13 @@ def load_library():
     L.dm_sac_polyak.argtypes = [vp, vp, C.c_longlong, f32, vp, vp]
     L.dm_rollout_finish_workspace_bytes.argtypes = [i32, i32]
     L.dm_rollout_finish.argtypes = [i32, i32, vp, vp, i32, vp, vp, C.c_double, C.c_double] + [vp] * 7 + [C.c_longlong, vp]
+    L.dm_render_create.argtypes = [vp, C.POINTER(vp)]
+    L.dm_render_destroy.argtypes = [vp]
+    L.dm_render_last_error.argtypes = [vp]
+    L.dm_render_last_error.restype = C.c_char_p
+    L.dm_render_kinematics.argtypes = [vp, vp, vp, i32, vp, vp, vp]
+    L.dm_render_cast.argtypes = [vp, vp, vp, i32, vp, i32, i32, vp, vp, vp, vp]
+    L.dm_render.argtypes = [vp, vp, vp, i32, vp, i32, i32, vp, vp, vp, vp, vp]
     for name in EXPORTS:
         if name not in ("dm_default_config", "dm_last_error"):
             getattr(L, name).restype = C.c_longlong if name in ("dm_policy_packed_floats", "dm_ppo_mlp_workspace_floats", "dm_ppo_wide_packed_elems", "dm_ppo_wide3_packed_elems", "dm_rollout_finish_workspace_bytes") else C.c_int

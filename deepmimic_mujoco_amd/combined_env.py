@@ -18,7 +18,7 @@ from .config import MotionConfig, RobotConfig
 from .deepmimic_env import _SimView
 from .mocap import MocapDM
 from .model import load_model, NU
-from .vec_env import Box, HipBatchEnv, HipSingleEnv, _LazyCombinedInfos, _action_space, _combined_info  # noqa: F401 (re-exported)
+from .vec_env import Box, HipBatchEnv, HipSingleEnv, _LazyCombinedInfos, _action_space, _check_renderer, _combined_info  # noqa: F401 (re-exported)
 
 NOBS_COMBINED = 72
 MOTION_WALK, MOTION_RUN, MOTION_GETUP, MOTION_TO_GETUP = 0, 1, 2, 3
@@ -139,15 +139,16 @@ class DPCombinedEnv(HipSingleEnv):
     ENV_CFG = DPCombinedEnvConfig()
     metadata = {"render.modes": []}
 
-    def __new__(cls, verbose=0, _profile=False, robot="unitree_g1", getup_motion="getup_facedown", device=0):
+    def __new__(cls, verbose=0, _profile=False, robot="unitree_g1", getup_motion="getup_facedown", device=0, renderer="stick"):
         if robot == "unitree_g1" and cls is DPCombinedEnv:   # the reference's own configuration (:165): the G1 engine
             from .g1 import G1CombinedEnv
-            return G1CombinedEnv(verbose=verbose, _profile=_profile, device=device)
+            return G1CombinedEnv(verbose=verbose, _profile=_profile, device=device, renderer=renderer)
         return super().__new__(cls)
 
-    def __init__(self, verbose=0, _profile=False, robot="unitree_g1", getup_motion="getup_facedown", device=0):
+    def __init__(self, verbose=0, _profile=False, robot="unitree_g1", getup_motion="getup_facedown", device=0, renderer="stick"):
         import torch
         self._torch = torch
+        self.renderer = _check_renderer(renderer)
         self.PROFILE = _profile
         self.verbose = verbose
         self.robot = robot
@@ -248,11 +249,11 @@ class HipCombinedVecEnv(HipBatchEnv):
         if robot == "unitree_g1" and cls is HipCombinedVecEnv:
             from .g1 import HipG1CombinedVecEnv
             return HipG1CombinedVecEnv(num_envs, device=device, seed=seed, auto_reset=auto_reset, sub_batches=kw.get("sub_batches", 1),
-                                       integrator=kw.get("integrator"))
+                                       integrator=kw.get("integrator"), renderer=kw.get("renderer", "stick"))
         return super().__new__(cls)
 
     def __init__(self, num_envs, robot="unitree_g1", getup_motion="getup_facedown", device=0, seed=1234,
-                 auto_reset=True, integrator=None):
+                 auto_reset=True, integrator=None, renderer="stick"):
         self.robot_config = RobotConfig(robot)
         model, cfg = load_model(self.robot_config.xml_path), self.ENV_CFG
 
@@ -263,7 +264,8 @@ class HipCombinedVecEnv(HipBatchEnv):
                                amnesty_steps=cfg.AMNESTY_STEPS, to_getup_len=MTToGetup.length, integrator=integrator)
             self.clips = _load_clips(e, model, robot, getup_motion)
             return e
-        super().__init__(num_envs, 1, make, model, NOBS_COMBINED, 8, NU, infos=_LazyCombinedInfos)   # one engine: no sub_batches here
+        super().__init__(num_envs, 1, make, model, NOBS_COMBINED, 8, NU, infos=_LazyCombinedInfos,
+                         renderer=renderer)   # one engine: no sub_batches here
 
     def motion_state(self):
         """(motion id int32[N], n_steps int32[N]) — `current_motion_mocap` / `current_motion_n_steps` per env."""

@@ -19,7 +19,7 @@ from . import _lib
 from .config import MotionConfig, RobotConfig
 from .mocap import MocapDM
 from .model import NOBS, NU, NV, load_model
-from .vec_env import Box, HipBatchEnv, HipImitationEnv, LazyInfos, _INFO_KEYS, _action_space, _make_info  # noqa: F401 (re-exported)
+from .vec_env import Box, HipBatchEnv, HipImitationEnv, LazyInfos, _INFO_KEYS, _action_space, _check_renderer, _make_info  # noqa: F401 (re-exported)
 
 
 class DPEnvConfig:
@@ -69,14 +69,15 @@ class DPEnv(HipImitationEnv):
     ENV_CFG = DPEnvConfig()
     metadata = {"render.modes": []}
 
-    def __new__(cls, motion=None, load_mocap=True, robot="humanoid3d", _profile=False, device=0):
+    def __new__(cls, motion=None, load_mocap=True, robot="humanoid3d", _profile=False, device=0, renderer="stick"):
         if robot == "unitree_g1" and cls is DPEnv:   # the second robot has its own engine (g1.py, csrc/dm_g1.hip)
             from .g1 import G1DPEnv
-            return G1DPEnv(motion=motion, load_mocap=load_mocap, robot=robot, _profile=_profile, device=device)
+            return G1DPEnv(motion=motion, load_mocap=load_mocap, robot=robot, _profile=_profile, device=device, renderer=renderer)
         return super().__new__(cls)
 
-    def __init__(self, motion=None, load_mocap=True, robot="humanoid3d", _profile=False, device=0):
+    def __init__(self, motion=None, load_mocap=True, robot="humanoid3d", _profile=False, device=0, renderer="stick"):
         import torch
+        self.renderer = _check_renderer(renderer)
         self.PROFILE = _profile
         self.motion_config = MotionConfig(motion=motion, robot=robot)
         self.robot_config = RobotConfig(robot=robot)
@@ -163,14 +164,16 @@ class HipDeepMimicVecEnv(HipBatchEnv):
 
     version, ENV_CFG = DPEnv.version, DPEnv.ENV_CFG
 
-    def __new__(cls, num_envs, motion=None, robot="humanoid3d", device=0, seed=1234, auto_reset=True, sub_batches=1, integrator=None):
+    def __new__(cls, num_envs, motion=None, robot="humanoid3d", device=0, seed=1234, auto_reset=True, sub_batches=1, integrator=None,
+                renderer="stick"):
         if robot == "unitree_g1" and cls is HipDeepMimicVecEnv:
             from .g1 import HipG1VecEnv
             return HipG1VecEnv(num_envs, motion=motion, device=device, seed=seed, auto_reset=auto_reset, sub_batches=sub_batches,
-                               integrator=integrator)
+                               integrator=integrator, renderer=renderer)
         return super().__new__(cls)
 
-    def __init__(self, num_envs, motion=None, robot="humanoid3d", device=0, seed=1234, auto_reset=True, sub_batches=1, integrator=None):
+    def __init__(self, num_envs, motion=None, robot="humanoid3d", device=0, seed=1234, auto_reset=True, sub_batches=1, integrator=None,
+                 renderer="stick"):
         import torch
         self.robot_config = RobotConfig(robot)
         model = load_model(self.robot_config.xml_path)
@@ -192,4 +195,4 @@ class HipDeepMimicVecEnv(HipBatchEnv):
                 ids = (torch.arange(nk, device=e.device) + k * nk) % len(self.motions)
                 e.set_env_clips(ids.to(torch.int32))
             return e
-        super().__init__(num_envs, sub_batches, make, model, NOBS, 5, NU)
+        super().__init__(num_envs, sub_batches, make, model, NOBS, 5, NU, renderer=renderer)

@@ -14,7 +14,7 @@ import numpy as np
 
 from . import mjcf, model as _model
 from ._lib import INTEGRATORS, EngineBase, load_library
-from .vec_env import Box, HipBatchEnv, HipImitationEnv, HipSingleEnv, _LazyCombinedInfos, _action_space, _combined_info
+from .vec_env import Box, HipBatchEnv, HipImitationEnv, HipSingleEnv, _LazyCombinedInfos, _action_space, _check_renderer, _combined_info
 from .config import RobotConfig
 
 NQ, NV, NU, NBODY, NGEOM, NJNT, NM, MAXPAIR, NOBS = 44, 43, 37, 39, 94, 38, 434, 1024, 85
@@ -319,7 +319,7 @@ class HipG1VecEnv(HipBatchEnv):
     when asked for ``robot="unitree_g1"``.  Actions are the policy's 23 values (src/deepmimic_env.py:303-307).
     ``motion`` may be a list (per-env clip id = env index mod len(list), as BASELINE config 5 mixes clips)."""
 
-    def __init__(self, num_envs, motion=None, device=0, seed=1234, auto_reset=True, sub_batches=1, integrator=None):
+    def __init__(self, num_envs, motion=None, device=0, seed=1234, auto_reset=True, sub_batches=1, integrator=None, renderer="stick"):
         from .deepmimic_env import DPEnvConfig
         motions = [motion] if (motion is None or isinstance(motion, str)) else list(motion)
         assert 1 <= len(motions) <= 8, "an engine holds up to 8 clips (DMG1_MAX_CLIPS)"
@@ -338,7 +338,7 @@ class HipG1VecEnv(HipBatchEnv):
                 ids = (e.torch.arange(nk, device=e.device) + k * nk) % len(pairs)
                 e.set_env_clips(ids.to(e.torch.int32).contiguous())
             return e
-        super().__init__(num_envs, sub_batches, make, load_g1_model()[0], NOBS, 5, NACT)
+        super().__init__(num_envs, sub_batches, make, load_g1_model()[0], NOBS, 5, NACT, renderer=renderer)
 
     def _step_engines(self, actions):
         """sub_batches > 1: every engine's launches go to its own HIP stream, forked from and joined back into the current one.
@@ -364,10 +364,11 @@ class G1DPEnv(HipImitationEnv):
     version = "v1.0"
     REASONS = REASONS      # the G1 table has reason 8, the run clip's roll / pitch limit
 
-    def __init__(self, motion=None, load_mocap=True, robot="unitree_g1", _profile=False, device=0, integrator=None):
+    def __init__(self, motion=None, load_mocap=True, robot="unitree_g1", _profile=False, device=0, integrator=None, renderer="stick"):
         import random
         import torch
         from .deepmimic_env import DPEnvConfig
+        self.renderer = _check_renderer(renderer)
         if robot != "unitree_g1":
             raise ValueError("G1DPEnv is the unitree_g1 environment")
         if not load_mocap:
@@ -421,7 +422,7 @@ class HipG1CombinedVecEnv(HipG1VecEnv):
     """N ``DPCombinedEnv()`` instances — the reference's training environment (src/sb3_ppo.py:277-278): Unitree G1, walk / run /
     getup / to_getup motion state machine, obs 98, 23 actions — as one HIP batch with SubprocVecEnv semantics."""
 
-    def __init__(self, num_envs, device=0, seed=1234, auto_reset=True, sub_batches=1, integrator=None):
+    def __init__(self, num_envs, device=0, seed=1234, auto_reset=True, sub_batches=1, integrator=None, renderer="stick"):
         self.mocaps = None
         self.robot_config = RobotConfig("unitree_g1")
 
@@ -431,7 +432,7 @@ class HipG1CombinedVecEnv(HipG1VecEnv):
             return e
         # action space = ctrlrange / ACT_SCALE (src/combined_env.py:196-200)
         HipBatchEnv.__init__(self, num_envs, sub_batches, make, load_g1_model()[0], NOBS_COMBINED, 8, NACT, act_scale=1.0 / 20.0,
-                             infos=_LazyCombinedInfos)
+                             infos=_LazyCombinedInfos, renderer=renderer)
         self.mocap = self.mocaps[0]
 
 
@@ -441,10 +442,11 @@ class G1CombinedEnv(HipSingleEnv):
 
     version = "v0.2.up"
 
-    def __init__(self, verbose=0, _profile=False, device=0, integrator=None):
+    def __init__(self, verbose=0, _profile=False, device=0, integrator=None, renderer="stick"):
         import random
         import torch
         from .combined_env import DPCombinedEnvConfig, MTToGetup, PAWalk
+        self.renderer = _check_renderer(renderer)
         self._torch, self._random, self.verbose = torch, random, verbose
         self.ENV_CFG = DPCombinedEnvConfig()
         self.robot = "unitree_g1"

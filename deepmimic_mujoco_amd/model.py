@@ -181,6 +181,7 @@ def compile_mjcf(xml_path: str | None = None) -> CompiledModel:
     oa = dict(opt.attrib) if opt is not None else {}
 
     m = CompiledModel()
+    m.xml_path = xml_path
     m.timestep = float(oa.get("timestep", 0.002))
     m.integrator = {"Euler": INT_EULER, "RK4": INT_RK4}[oa.get("integrator", "Euler")]
     if oa.get("solver", "Newton") != "PGS":

@@ -56,6 +56,8 @@ def build_parser():
                     help="> 0: batched deterministic evaluation (evaluation.py) on that many auto_reset=False envs on rank 0: at every "
                          "--eval-every point (eval_batch.csv) and once after training (\"eval\" of the --json line); finished envs leave "
                          "the launches on either robot (compact=\"all\"); 0 = off")
+    ap.add_argument("--renderer", default="stick", choices=["stick", "raycast"],
+                    help="frames of the eval dashboard: host-side stick figure, or ray-cast on the device (raycast.py)")
     ap.add_argument("--run-name", default="run")
     ap.add_argument("--eval-dir", default="~/deep_mimic")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
@@ -126,10 +128,10 @@ def main(argv=None):
         from .eval_dashboard import EvalDashboardCallback
         if args.env == "dp_combined_env":
             from .combined_env import DPCombinedEnv
-            eval_env = DPCombinedEnv(robot=args.robot, device=local_rank)
+            eval_env = DPCombinedEnv(robot=args.robot, device=local_rank, renderer=args.renderer)
         else:
             from .deepmimic_env import DPEnv
-            eval_env = DPEnv(motions[0], robot=args.robot, device=local_rank)
+            eval_env = DPEnv(motions[0], robot=args.robot, device=local_rank, renderer=args.renderer)
         dash = EvalDashboardCallback(eval_env, args.motion + "_" + args.run_name, every_n_global_steps=args.eval_every, out_root=args.eval_dir,
                                      batch_env=batch_env)
 
@@ -188,10 +190,10 @@ def _train_sac(args, env, motions, local_rank):
         from .eval_dashboard import EvalDashboardCallback
         if args.env == "dp_combined_env":
             from .combined_env import DPCombinedEnv
-            eval_env = DPCombinedEnv(robot=args.robot, device=local_rank)
+            eval_env = DPCombinedEnv(robot=args.robot, device=local_rank, renderer=args.renderer)
         else:
             from .deepmimic_env import DPEnv
-            eval_env = DPEnv(motions[0], robot=args.robot, device=local_rank)
+            eval_env = DPEnv(motions[0], robot=args.robot, device=local_rank, renderer=args.renderer)
         dash = EvalDashboardCallback(eval_env, args.motion + "_" + args.run_name, every_n_global_steps=args.eval_every, out_root=args.eval_dir,
                                      batch_env=batch_env)
 

@@ -79,6 +79,50 @@ def _combined_info(terms, reason, reasons=_lib.REASONS):
     return info
 
 
+RENDERERS = ("stick", "raycast")
+FRAME_W, FRAME_H = 320, 240          # what render() returns, either renderer
+
+
+def _check_renderer(renderer):
+    if renderer not in RENDERERS:
+        raise ValueError("renderer must be one of %s, got %r" % (RENDERERS, renderer))
+    return renderer
+
+
+class _RayCastSurface:
+    """``renderer="raycast"`` of the environment classes: frames cast on the device (raycast.RayRenderer) from the state that
+    ``get_state`` returns.  No forward evaluation runs and no warm start is touched, so the next step does not depend on whether a
+    frame was rendered.  The owner sets ``renderer`` and provides ``_render_engines()``."""
+
+    renderer = "stick"
+    _ray = None
+
+    def _ray_renderer(self):
+        if self._ray is None:
+            from .raycast import RayRenderer
+            self._ray = RayRenderer(self.model, device=self._render_engines()[0].device.index or 0)
+        return self._ray
+
+    def _render_qpos(self):
+        q = [e.get_state()[0] for e in self._render_engines()]
+        return q[0] if len(q) == 1 else self._torch.cat(q)
+
+    def render_batch(self, env_ids=None, width=FRAME_W, height=FRAME_H, camera=None, rgb=True, depth=False, segmentation=False):
+        """Frames of the listed envs (all without a list) as device tensors: ``rgb`` uint8 [n, H, W, 3], ``depth`` float32
+        [n, H, W] (metres along the view axis, inf = sky), ``segmentation`` int32 [n, H, W] (model geom id, -1 = sky)."""
+        if self.renderer != "raycast":
+            raise RuntimeError('render_batch needs renderer="raycast"')
+        return self._ray_renderer().render(self._render_qpos(), camera, width, height, env_ids=env_ids, rgb=rgb, depth=depth,
+                                           segmentation=segmentation)
+
+    def _raycast_frame(self, mode):
+        """``render(mode)`` of env 0: "rgb_array" (or None) -> uint8 [240, 320, 3]; "depth_array" -> float32 [240, 320]."""
+        if mode not in (None, "rgb_array", "depth_array"):
+            raise ValueError("render mode %r" % (mode,))
+        key = "depth" if mode == "depth_array" else "rgb"
+        return self.render_batch([0], rgb=key == "rgb", depth=key == "depth")[key][0].cpu().numpy()
+
+
 class LazyInfos(list):
     """`infos` of a VecEnv step: a real ``list`` (SB3's wrappers slice it, assign into it and test it with
     ``isinstance(infos, (list, tuple))``) whose dicts are built on first access — 4096 dicts per step would dominate the
@@ -157,7 +201,7 @@ class _LazyCombinedInfos(LazyInfos):
     _make = staticmethod(_combined_info)
 
 
-class HipBatchEnv(_SB3VecEnv):
+class HipBatchEnv(_RayCastSurface, _SB3VecEnv):
     """N environments as one HIP batch with SubprocVecEnv semantics (auto-reset, ``terminal_observation``).
 
     ``sub_batches`` > 1: independent engines over contiguous env ranges, so a rollout can keep one range simulating while the
@@ -165,10 +209,12 @@ class HipBatchEnv(_SB3VecEnv):
     output tensors; every engine writes its contiguous block of rows (``sub_out[k]`` are views of ``out`` at ``sub_slices[k]``).
     ``step_tensor`` / ``reset_tensor`` / ``step_sub`` are the zero-copy paths used by deepmimic_mujoco_amd.ppo."""
 
-    def __init__(self, num_envs, sub_batches, make_engine, model, obs_dim, terms_dim, n_actions, act_scale=1.0, infos=LazyInfos):
+    def __init__(self, num_envs, sub_batches, make_engine, model, obs_dim, terms_dim, n_actions, act_scale=1.0, infos=LazyInfos,
+                 renderer="stick"):
         """``make_engine(nk, k)`` builds the engine of sub-batch ``k`` (``nk`` envs, clips loaded); ``infos`` is the LazyInfos class."""
         import torch
         self._torch = torch
+        self.renderer = _check_renderer(renderer)
         self.num_envs, self.sub_batches = int(num_envs), int(sub_batches)
         assert self.sub_batches >= 1 and self.num_envs % self.sub_batches == 0
         nk = self.num_envs // self.sub_batches
@@ -250,6 +296,8 @@ class HipBatchEnv(_SB3VecEnv):
         return self.step_wait()
 
     def close(self):
+        if self._ray is not None:
+            self._ray.close()
         for e in getattr(self, "engines", []):
             e.close()
 
@@ -287,19 +335,29 @@ class HipBatchEnv(_SB3VecEnv):
     def unwrapped(self):
         return self
 
+    def _render_engines(self):
+        return self.engines
+
     def get_images(self):
         """One frame per env in SB3; a 4 096-tile mosaic is of no use: the frame of env 0 stands for the batch."""
         return [self.render(mode="rgb_array")]
 
     def render(self, mode=None):
         """Software stick figure (render.py) of env 0 of the batch, 240 x 320 x 3 uint8 (what VecVideoRecorder-style callers
-        get).  ``body_xpos`` puts the warm start back: rendering is not physics."""
+        get).  ``body_xpos`` puts the warm start back: rendering is not physics.  With ``renderer="raycast"``: the ray-cast frame of
+        env 0 (``mode="depth_array"``: its depth image)."""
+        if self.renderer == "raycast":
+            return self._raycast_frame(mode)
         from .render import stick_figure
         return stick_figure(self.engine.body_xpos(), self.model.body_parent)
 
 
-class HipSingleEnv:
-    """gym.Env plumbing of one environment of a batch engine (``self._eng``, one env, outputs in ``self._out``)."""
+class HipSingleEnv(_RayCastSurface):
+    """gym.Env plumbing of one environment of a batch engine (``self._eng``, one env, outputs in ``self._out``); a subclass that
+    takes the ``renderer`` keyword sets ``self.renderer``."""
+
+    def _render_engines(self):
+        return [self._eng]
 
     def _i32(self, v):
         t = self._torch
@@ -330,11 +388,16 @@ class HipSingleEnv:
         self._eng.set_state(self._row(qpos), self._row(qvel), run_forward=True)
 
     def render(self, mode=None):
-        """Software stick figure (render.py) of the current body poses: there is no MuJoCo viewer behind this env."""
+        """Software stick figure (render.py) of the current body poses: there is no MuJoCo viewer behind this env.  With
+        ``renderer="raycast"``: the ray-cast frame (``mode="depth_array"``: the depth image)."""
+        if self.renderer == "raycast":
+            return self._raycast_frame(mode)
         from .render import stick_figure
         return stick_figure(self._eng.body_xpos(), self.model.body_parent)
 
     def close(self):
+        if self._ray is not None:
+            self._ray.close()
         self._eng.close()
 
 
