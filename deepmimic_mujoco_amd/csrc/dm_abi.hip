@@ -2,8 +2,7 @@
 // Builds the fp32 device tables from DmModel, owns the per-env HBM state rows and
 // the clip tables, and launches the fused step kernel (dm_kernels.hip).
 #include "../../include/deepmimic_hip.h"
-#include "dm_device.h"
-#include "dm_topology.h"
+#include "dm_tables_host.h"   // check_model, build_tables, pack_clip; dm_host.h: DmHost, HIPCHK, DM_DEVICE, DM_LAUNCH
 
 #include <math.h>
 #include <stdio.h>
@@ -14,7 +13,7 @@
 
 #include "dm_kernels.hip"
 
-struct DmEngine {
+struct DmEngine : DmHost {
   DmConfig cfg;
   DmModel model;
   int N = 0;
@@ -36,21 +35,7 @@ struct DmEngine {
   int waves = 0;                               // 0: kernel variant from the batch size; 2 / 3: forced (env DM_WAVES, experiments)
   bool timing = false;
   float last_ms = 0;
-  std::string err;
 };
-
-static int fail(DmEngine *e, int code, const char *what, hipError_t he = hipSuccess) {
-  if (e) {
-    e->err = what;
-    if (he != hipSuccess) { e->err += ": "; e->err += hipGetErrorString(he); }
-  }
-  return code;
-}
-#define HIPCHK(e, call)                                   \
-  do {                                                    \
-    hipError_t _r = (call);                               \
-    if (_r != hipSuccess) return fail(e, DM_EHIP, #call, _r); \
-  } while (0)
 
 extern "C" void dm_default_config(DmConfig *c) {
   memset(c, 0, sizeof(*c));
@@ -71,177 +56,48 @@ extern "C" void dm_default_config(DmConfig *c) {
   c->integrator = DM_CFG_INT_MODEL;   // the XML's (RK4, xml :9)
 }
 
-static void build_tables(const DmModel &m, DmDev &T) {
-  memset(&T, 0, sizeof(T));
-  T.timestep = (float)m.timestep;
-  T.tolerance = (float)m.tolerance;
-  T.pgs_scale = (float)(1.0 / (m.meaninertia * (DM_NV > 1 ? DM_NV : 1)));
-  for (int i = 0; i < 3; i++) T.gravity[i] = (float)m.gravity[i];
-  double tc = fmax(m.solref[0], 2 * m.timestep), dr = m.solref[1], dmax = m.solimp[1];
-  T.K = (float)(1.0 / fmax(1e-15, dmax * dmax * tc * tc * dr * dr));
-  T.B = (float)(2.0 / fmax(1e-15, dmax * tc));
-  for (int i = 0; i < 5; i++) T.solimp[i] = (float)m.solimp[i];
-  double mt = 0;
-  for (int b = 0; b < DM_NBODY; b++) mt += m.body_mass[b];
-  T.total_mass_inv = (float)(1.0 / mt);
-  for (int i = 0; i < DM_NQ; i++) T.qpos0[i] = (float)m.qpos0[i];
-  T.iterations = m.iterations;
-  T.npair = m.npair;
-  T.torso_body = m.torso_body; T.rfoot_geom = m.rfoot_geom; T.lfoot_geom = m.lfoot_geom; T.floor_geom = m.floor_geom;
-  for (int i = 0; i < 4; i++) T.ee_geom[i] = m.ee_geom[i];
-  for (int b = 0; b < DM_NBODY; b++) {
-    T.b_parent[b] = m.body_parent[b]; T.b_depth[b] = m.body_depth[b];
-    T.b_dofadr[b] = m.body_dofadr[b] < 0 ? 0 : m.body_dofadr[b]; T.b_dofnum[b] = m.body_dofnum[b];
-    for (int i = 0; i < 3; i++) { T.b_pos[b][i] = (float)m.body_pos[b][i]; T.b_ipos[b][i] = (float)m.body_ipos[b][i]; }
-    for (int i = 0; i < 6; i++) T.b_inertia[b][i] = (float)m.body_inertia[b][i];
-    T.b_mass[b] = (float)m.body_mass[b];
-    T.b_invw[b] = (float)m.body_invweight0[b][0];
-    uint32_t sub = 0;
-    for (int c = 1; c < DM_NBODY; c++) {
-      int a = c;
-      while (a > 0 && a != b) a = m.body_parent[a];
-      if (a == b && b > 0) sub |= 1u << c;
-    }
-    T.b_subtree[b] = sub;
-    uint64_t chain = 0;
-    for (int a = b; a > 0; a = m.body_parent[a])
-      for (int k = 0; k < m.body_dofnum[a]; k++) chain |= 1ull << (m.body_dofadr[a] + k);
-    T.b_chain[b] = chain;
-    uint32_t cb = 0;
-    int ids[8], nc = 0;
-    for (int a = b; a > 0; a = m.body_parent[a]) ids[nc++] = a;
-    for (int c = 0; c < nc && c < 4; c++) cb |= (uint32_t)ids[nc - 1 - c] << (8 * c);   // root first
-    T.b_chainb[b] = cb;
-  }
-  for (int k = 0; k < DM_NV; k++) {
-    int j = m.dof_jnt[k];
-    T.d_body[k] = m.dof_body[k];
-    T.d_act[k] = -1;
-    T.d_limited[k] = (m.jnt_type[j] == DM_JNT_HINGE) ? m.jnt_limited[j] : 0;
-    for (int i = 0; i < 3; i++) T.d_axis[k][i] = (float)m.jnt_axis[j][i];
-    T.d_arm[k] = (float)m.dof_armature[k]; T.d_damp[k] = (float)m.dof_damping[k];
-    T.d_invw[k] = (float)m.dof_invweight0[k];
-    T.d_lo[k] = (float)m.jnt_range[j][0]; T.d_hi[k] = (float)m.jnt_range[j][1];
-    int n = 0;
-    for (int a = m.dof_parent[k]; a >= 0 && n < DMK_MAXANC; a = m.dof_parent[a]) T.d_anc[k][n++] = (uint8_t)a;
-    T.d_nanc[k] = n;
-    for (int d = 0; d < n; d++) T.d_ancabs[k][d] = T.d_anc[k][n - 1 - d];   // absolute depth d
-    T.d_pbody[k] = m.body_parent[m.dof_body[k]];
-  }
-  for (int k = 0; k < DM_NV; k++) {
-    for (int a = 0; a < T.d_nanc[k]; a++) T.d_desc[T.d_anc[k][a]] |= 1ull << k;
-    T.nanc_pack[k >> 4] |= (uint64_t)T.d_nanc[k] << (4 * (k & 15));
-    for (int a = 0; a < T.d_nanc[k]; a++) T.d_ancm[k] |= 1ull << T.d_anc[k][a];
-    T.d_madr[k] = m.dof_Madr[k];
-  }
-  for (int a = 0; a < DM_NU; a++) {
-    int k = m.act_dof[a];
-    T.d_act[k] = a; T.d_gear[k] = (float)m.act_gear[a];
-    T.d_clo[k] = (float)m.act_ctrlrange[a][0]; T.d_chi[k] = (float)m.act_ctrlrange[a][1];
-  }
-  for (int g = 0; g < DM_NGEOM; g++) {
-    T.g_body[g] = m.geom_body[g]; T.g_type[g] = m.geom_type[g]; T.g_condim[g] = m.geom_condim[g];
-    for (int i = 0; i < 3; i++) { T.g_pos[g][i] = (float)m.geom_pos[g][i]; T.g_size[g][i] = (float)m.geom_size[g][i]; }
-    const double *q = m.geom_quat[g];
-    double w = q[0], x = q[1], y = q[2], z = q[3];
-    double M[9] = {w * w + x * x - y * y - z * z, 2 * (x * y - w * z), 2 * (x * z + w * y),
-                   2 * (x * y + w * z), w * w - x * x + y * y - z * z, 2 * (y * z - w * x),
-                   2 * (x * z - w * y), 2 * (y * z + w * x), w * w - x * x - y * y + z * z};
-    for (int i = 0; i < 9; i++) T.g_mat[g][i] = (float)M[i];
-    T.g_rbound[g] = (float)m.geom_rbound[g]; T.g_margin[g] = (float)m.geom_margin[g];
-    T.g_mu[g] = (float)m.geom_friction[g][0];
-  }
-  for (int p = 0; p < DM_MAXPAIR; p++) { T.p_g1[p] = (int16_t)m.pair_geom1[p]; T.p_g2[p] = (int16_t)m.pair_geom2[p]; }
-  for (int p = 0; p < m.npair; p++) {
-    int g1 = m.pair_geom1[p], g2 = m.pair_geom2[p];
-    DmPairDev &pr = T.pairs[p];
-    pr.g1 = (int16_t)g1; pr.g2 = (int16_t)g2;
-    pr.t1 = (int8_t)m.geom_type[g1]; pr.t2 = (int8_t)m.geom_type[g2];
-    pr.margin = (float)fmax(m.geom_margin[g1], m.geom_margin[g2]);
-    pr.rbsum = (float)((m.geom_type[g1] == DM_GEOM_PLANE ? 0.0 : m.geom_rbound[g1]) + m.geom_rbound[g2]);
-    for (int i = 0; i < 3; i++) { pr.z1[i] = (float)m.geom_size[g1][i]; pr.z2[i] = (float)m.geom_size[g2][i]; }
-  }
-  int p = 0;
-  for (int b = 0; b < DMK_MAXANC; b++)
-    for (int a = 0; a <= b; a++) { T.tri_a[p] = (uint8_t)a; T.tri_b[p] = (uint8_t)b; p++; }
-  dm_build_lane_records(T);   // T.rec: the per-lane copies the step kernels load a phase ahead (dm_tables.h)
-}
-
-static int check_model(DmEngine *e, const DmModel &m) {
-  if (m.nq != DM_NQ || m.nv != DM_NV || m.nu != DM_NU || m.nbody != DM_NBODY || m.ngeom != DM_NGEOM)
-    return fail(e, DM_EINVAL, "model dimensions do not match the compiled-in humanoid3d dimensions");
-  if (m.integrator != DM_INT_RK4 && m.integrator != DM_INT_EULER) return fail(e, DM_EINVAL, "integrator must be RK4 or Euler");
-  if (m.npair < 0 || m.npair > DM_MAXPAIR) return fail(e, DM_EINVAL, "npair out of range");
-  for (int b = 1; b < DM_NBODY; b++) {
-    if (m.body_quat[b][0] != 1.0) return fail(e, DM_EINVAL, "kernels assume identity body quaternions");
-    if (m.body_dofnum[b] != 1 && m.body_dofnum[b] != 3 && m.body_dofnum[b] != 6)
-      return fail(e, DM_EINVAL, "kernels assume 1- or 3-hinge bodies under a free root");
-    if (m.body_depth[b] < 1 || m.body_depth[b] > 4) return fail(e, DM_EINVAL, "tree depth > 4");
-  }
-  for (int j = 0; j < DM_NJNT; j++)
-    for (int i = 0; i < 3; i++)
-      if (m.jnt_pos[j][i] != 0.0) return fail(e, DM_EINVAL, "kernels assume joint anchors at the body origin");
-  if (m.jnt_type[0] != DM_JNT_FREE || m.jnt_body[0] != 1) return fail(e, DM_EINVAL, "joint 0 must be the free root");
-  for (int k = 0; k < DM_NV; k++)
-    if (m.dof_parent[k] != topo::PARENT[k] || m.dof_Madr[k] != topo::MADR[k])
-      return fail(e, DM_EINVAL, "dof tree differs from the compiled-in topology (regenerate csrc/dm_topology.h)");
-  for (int b = 0; b < DM_NBODY; b++)
-    if (m.body_parent[b] != topo::BPARENT[b])
-      return fail(e, DM_EINVAL, "body tree differs from the compiled-in topology (regenerate csrc/dm_topology.h)");
+// Everything dm_create puts on the device.  On failure e->err says why and the caller deletes e, which frees what was made.
+static int dm_init(DmEngine *e) {
+  const DmModel &m = e->model;
+  if (check_model(m, e->err) != DM_OK) return DM_EINVAL;
+  DM_DEVICE(e);
+  DmDev T;
+  build_tables(m, T);
+  HIPCHK(e, e->alloc(&e->dT, 1));
+  HIPCHK(e, e->upload(e->dT, &T, 1));
+  const size_t N = (size_t)e->N;
+  std::vector<float> init(N * DMK_STATE_STRIDE, 0.f);
+  for (size_t i = 0; i < N; i++)
+    for (int k = 0; k < DM_NQ; k++) init[i * DMK_STATE_STRIDE + DMS_QPOS + k] = (float)m.qpos0[k];
+  HIPCHK(e, e->alloc(&e->dState, init.size()));
+  HIPCHK(e, e->upload(e->dState, init.data(), init.size()));
+  HIPCHK(e, e->alloc(&e->dArScratch, N * DMK_MAXROW * DMK_MAXROW));
+  HIPCHK(e, e->alloc(&e->dCost, N));
+  HIPCHK(e, e->fill(e->dCost, 0, N * sizeof(int32_t)));
+  std::vector<int32_t> ident(N);
+  for (size_t i = 0; i < N; i++) ident[i] = (int32_t)i;
+  HIPCHK(e, e->alloc(&e->dOrder, N));
+  HIPCHK(e, e->upload(e->dOrder, ident.data(), N));   // until the first dm_step schedules
+  for (int i = 0; i < DmEngine::NEV; i++) { HIPCHK(e, e->event(&e->ev0[i])); HIPCHK(e, e->event(&e->ev1[i])); }
   return DM_OK;
 }
 
 extern "C" int dm_create(const DmModel *model, const DmConfig *cfg, DmHandle *out) {
   if (!model || !cfg || !out || cfg->num_envs < 1) return DM_EINVAL;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return DM_ENODEV;
+  if (!dm_have_device()) return DM_ENODEV;
   DmEngine *e = new DmEngine();
   e->cfg = *cfg;
   e->model = *model;
+  e->device = cfg->device;
   e->N = cfg->num_envs;
   if (const char *w = getenv("DM_WAVES")) e->waves = atoi(w);
-  int rc = check_model(e, *model);
+  const int rc = dm_init(e);
   if (rc != DM_OK) { fprintf(stderr, "dm_create: %s\n", e->err.c_str()); delete e; return rc; }
-  if (hipSetDevice(cfg->device) != hipSuccess) { delete e; return DM_ENODEV; }
-  DmDev T;
-  build_tables(*model, T);
-  if (hipMalloc(&e->dT, sizeof(DmDev)) != hipSuccess) { delete e; return DM_ENOMEM; }
-  hipMemcpy(e->dT, &T, sizeof(DmDev), hipMemcpyHostToDevice);
-  size_t sb = (size_t)e->N * DMK_STATE_STRIDE * sizeof(float);
-  if (hipMalloc(&e->dState, sb) != hipSuccess) { hipFree(e->dT); delete e; return DM_ENOMEM; }
-  std::vector<float> init((size_t)e->N * DMK_STATE_STRIDE, 0.f);
-  for (int i = 0; i < e->N; i++)
-    for (int k = 0; k < DM_NQ; k++) init[(size_t)i * DMK_STATE_STRIDE + DMS_QPOS + k] = (float)model->qpos0[k];
-  hipMemcpy(e->dState, init.data(), sb, hipMemcpyHostToDevice);
-  if (hipMalloc(&e->dArScratch, (size_t)e->N * DMK_MAXROW * DMK_MAXROW * sizeof(float)) != hipSuccess) {
-    hipFree(e->dState); hipFree(e->dT); delete e; return DM_ENOMEM;
-  }
-  if (hipMalloc(&e->dOrder, e->N * sizeof(int32_t)) != hipSuccess || hipMalloc(&e->dCost, e->N * sizeof(int32_t)) != hipSuccess) {
-    hipFree(e->dArScratch); hipFree(e->dState); hipFree(e->dT); delete e; return DM_ENOMEM;
-  }
-  hipMemset(e->dCost, 0, e->N * sizeof(int32_t));
-  { std::vector<int32_t> ident(e->N);
-    for (int i = 0; i < e->N; i++) ident[i] = i;
-    hipMemcpy(e->dOrder, ident.data(), e->N * sizeof(int32_t), hipMemcpyHostToDevice); }   // until the first dm_step schedules
-  for (int i = 0; i < DmEngine::NEV; i++) { hipEventCreate(&e->ev0[i]); hipEventCreate(&e->ev1[i]); }
   *out = e;
   return DM_OK;
 }
 
-extern "C" int dm_destroy(DmHandle e) {
-  if (!e) return DM_EINVAL;
-  hipSetDevice(e->cfg.device);
-  hipDeviceSynchronize();
-  for (int i = 0; i < DM_MAX_CLIPS; i++) { if (e->dClipRows[i]) hipFree(e->dClipRows[i]); if (e->dClipReset[i]) hipFree(e->dClipReset[i]); }
-  if (e->dState) hipFree(e->dState);
-  if (e->dArScratch) hipFree(e->dArScratch);
-  if (e->dOrder) hipFree(e->dOrder);
-  if (e->dCost) hipFree(e->dCost);
-  if (e->dT) hipFree(e->dT);
-  for (int i = 0; i < DmEngine::NEV; i++) { if (e->ev0[i]) hipEventDestroy(e->ev0[i]); if (e->ev1[i]) hipEventDestroy(e->ev1[i]); }
-  delete e;
-  return DM_OK;
-}
+extern "C" int dm_destroy(DmHandle e) { return dm_destroy_engine(e); }
 
 extern "C" const char *dm_last_error(DmHandle e) { return e ? e->err.c_str() : "null handle"; }
 extern "C" int dm_num_envs(DmHandle e) { return e ? e->N : DM_EINVAL; }
@@ -251,35 +107,12 @@ extern "C" int dm_terms_dim(DmHandle e) { return e ? (e->cfg.task == DM_TASK_COM
 extern "C" int dm_load_clip(DmHandle e, int clip_id, int L, const double *qpos, const double *qvel,
                             const double *body_xpos, const double *geom_xpos) {
   if (!e || clip_id < 0 || clip_id >= DM_MAX_CLIPS || L < 1 || !qpos || !qvel || !body_xpos || !geom_xpos)
-    return fail(e, DM_EINVAL, "dm_load_clip: bad argument");
-  HIPCHK(e, hipSetDevice(e->cfg.device));
-  const DmModel &m = e->model;
+    return dm_fail(e, DM_EINVAL, "dm_load_clip: bad argument");
+  DM_DEVICE(e);
   std::vector<float> rows((size_t)L * DMK_CLIP_ROW, 0.f), reset((size_t)L * DMK_RESET_ROW, 0.f);
-  double mt = 0;
-  for (int b = 0; b < DM_NBODY; b++) mt += m.body_mass[b];
-  for (int f = 0; f < L; f++) {
-    float *r = &rows[(size_t)f * DMK_CLIP_ROW];
-    const double *q = qpos + (size_t)f * DM_NQ, *v = qvel + (size_t)f * DM_NV;
-    for (int i = 0; i < 28; i++) { r[i] = (float)q[7 + i]; r[28 + i] = (float)v[6 + i]; }
-    for (int i = 0; i < 4; i++) r[56 + i] = (float)q[3 + i];
-    for (int ee = 0; ee < 4; ee++)
-      for (int i = 0; i < 3; i++) r[60 + 3 * ee + i] = (float)geom_xpos[((size_t)f * DM_NGEOM + m.ee_geom[ee]) * 3 + i];
-    for (int i = 0; i < 3; i++) {
-      double c = 0;
-      for (int b = 0; b < DM_NBODY; b++) c += body_xpos[((size_t)f * DM_NBODY + b) * 3 + i] * m.body_mass[b];
-      r[72 + i] = (float)(c / mt);
-      r[75 + i] = (float)q[i];
-    }
-    r[78] = (float)v[0]; r[79] = (float)v[1];   // root linear velocity xy (DPCombinedEnv task reward)
-    float *rr = &reset[(size_t)f * DMK_RESET_ROW];
-    for (int i = 0; i < DM_NQ; i++) rr[i] = (float)q[i];
-    for (int i = 0; i < DM_NV; i++) rr[35 + i] = (float)v[i];
-  }
-  if (e->dClipRows[clip_id]) { hipFree(e->dClipRows[clip_id]); hipFree(e->dClipReset[clip_id]); }
-  HIPCHK(e, hipMalloc(&e->dClipRows[clip_id], rows.size() * sizeof(float)));
-  HIPCHK(e, hipMalloc(&e->dClipReset[clip_id], reset.size() * sizeof(float)));
-  HIPCHK(e, hipMemcpy(e->dClipRows[clip_id], rows.data(), rows.size() * sizeof(float), hipMemcpyHostToDevice));
-  HIPCHK(e, hipMemcpy(e->dClipReset[clip_id], reset.data(), reset.size() * sizeof(float), hipMemcpyHostToDevice));
+  pack_clip(e->model, L, qpos, qvel, body_xpos, geom_xpos, rows.data(), reset.data());
+  e->clipL[clip_id] = 0;   // an empty slot if the reload fails
+  HIPCHK(e, e->reload({{&e->dClipRows[clip_id], &rows}, {&e->dClipReset[clip_id], &reset}}));
   e->clipL[clip_id] = L;
   return DM_OK;
 }
@@ -320,9 +153,8 @@ __global__ void dm_get_state_kernel(const float *state, const int32_t *ids, int 
 
 extern "C" int dm_get_env_clips(DmHandle e, int32_t *clip_ids, void *stream) {
   if (!e || !clip_ids) return DM_EINVAL;
-  HIPCHK(e, hipSetDevice(e->cfg.device));
-  hipLaunchKernelGGL(dm_get_clip_kernel, dim3((e->N + 255) / 256), dim3(256), 0, (hipStream_t)stream, e->dState, clip_ids, e->N);
-  HIPCHK(e, hipGetLastError());
+  DM_DEVICE(e);
+  DM_LAUNCH(e, dm_get_clip_kernel, dim3((e->N + 255) / 256), dim3(256), 0, (hipStream_t)stream, e->dState, clip_ids, e->N);
   return DM_OK;
 }
 
@@ -334,9 +166,8 @@ extern "C" int dm_set_clip_flags(DmHandle e, int clip_id, int flags) {
 
 extern "C" int dm_set_env_clips(DmHandle e, const int32_t *clip_ids, void *stream) {
   if (!e) return DM_EINVAL;
-  HIPCHK(e, hipSetDevice(e->cfg.device));
-  hipLaunchKernelGGL(dm_set_clip_kernel, dim3((e->N + 255) / 256), dim3(256), 0, (hipStream_t)stream, e->dState, clip_ids, e->N);
-  HIPCHK(e, hipGetLastError());
+  DM_DEVICE(e);
+  DM_LAUNCH(e, dm_set_clip_kernel, dim3((e->N + 255) / 256), dim3(256), 0, (hipStream_t)stream, e->dState, clip_ids, e->N);
   return DM_OK;
 }
 
@@ -359,29 +190,34 @@ static void fill_launch(DmEngine *e, DmLaunch &P, int mode) {
 // variant_n: the batch size the two- / three-wave choice is made for (0: nslots)
 static int launch(DmEngine *e, DmLaunch &P, int nslots, void *stream, int variant_n = 0) {
   P.nslots = nslots;
-  if (e->clipL[0] < 1) return fail(e, DM_EINVAL, "no clip loaded (dm_load_clip clip 0 first)");
-  if (e->cfg.task == DM_TASK_COMBINED && (e->clipL[1] < 1 || e->clipL[2] < 2))
-    return fail(e, DM_EINVAL, "combined task needs clips 0,1,2 = walk, run, getup");
-  HIPCHK(e, hipSetDevice(e->cfg.device));
+  if (const char *why = dm_clips_missing(e->clipL, e->cfg.task == DM_TASK_COMBINED, false)) return dm_fail(e, DM_EINVAL, why);
+  DM_DEVICE(e);
   hipStream_t s = (hipStream_t)stream;
   const int evi = (int)(e->nrec % DmEngine::NEV);
   const bool rec = e->timing && (e->nlaunch++ % e->stride) == 0;
-  if (rec) hipEventRecord(e->ev0[evi], s);
+  if (rec) HIPCHK(e, hipEventRecord(e->ev0[evi], s));
   const dim3 grid((P.nslots + DMK_ENVS_PER_BLOCK - 1) / DMK_ENVS_PER_BLOCK), block(64 * DMK_ENVS_PER_BLOCK);
+  // three waves per SIMD (168 VGPRs): faster than the two-wave build from 3 072 envs up since r2 (per-stage laundering of
+  // the lane id: no hoisted lane-compare masks spilled across the stage loop): 13.4 vs 12.9 M at 4 096 envs, 21.4 vs
+  // 17.5 M at 65 536
   const bool three_waves = e->waves == 3 || (e->waves == 0 && (variant_n > 0 ? variant_n : P.nslots) >= 3072);
   if (e->cfg.task == DM_TASK_COMBINED) {
-    if (three_waves) hipLaunchKernelGGL(dm_step_combined_kernel_w3, grid, block, 0, s, P);
-    else hipLaunchKernelGGL(dm_step_combined_kernel, grid, block, 0, s, P);
+    if (three_waves) DM_LAUNCH(e, dm_step_combined_kernel_w3, grid, block, 0, s, P);
+    else DM_LAUNCH(e, dm_step_combined_kernel, grid, block, 0, s, P);
   } else if (three_waves) {
-    // three waves per SIMD (168 VGPRs): faster than the two-wave build from 3 072 envs up since r2 (per-stage laundering of
-    // the lane id: no hoisted lane-compare masks spilled across the stage loop): 13.4 vs 12.9 M at 4 096 envs, 21.4 vs
-    // 17.5 M at 65 536
-    hipLaunchKernelGGL(dm_step_kernel_w3, grid, block, 0, s, P);
+    DM_LAUNCH(e, dm_step_kernel_w3, grid, block, 0, s, P);
   } else {
-    hipLaunchKernelGGL(dm_step_kernel, grid, block, 0, s, P);
+    DM_LAUNCH(e, dm_step_kernel, grid, block, 0, s, P);
   }
-  if (rec) { hipEventRecord(e->ev1[evi], s); e->nrec++; }
-  HIPCHK(e, hipGetLastError());
+  if (rec) { HIPCHK(e, hipEventRecord(e->ev1[evi], s)); e->nrec++; }
+  return DM_OK;
+}
+// the longest-first launch order of a step from this state: the work estimates of the last dm_step
+static int schedule(DmEngine *e, DmLaunch &P, void *stream) {
+  if (!e->cfg.lpt_schedule) return DM_OK;
+  DM_DEVICE(e);
+  DM_LAUNCH(e, dm_schedule_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, e->dCost, e->dOrder, e->N);
+  P.env_ids = e->dOrder;
   return DM_OK;
 }
 
@@ -395,22 +231,18 @@ extern "C" int dm_reset(DmHandle e, const uint8_t *mask, const int32_t *idx_init
 
 extern "C" int dm_step(DmHandle e, const float *actions, float *obs, float *rew, uint8_t *done, float *terms,
                        int32_t *reason, float *terminal_obs, void *stream) {
-  if (!e || !actions || !obs || !rew || !done) return fail(e, DM_EINVAL, "dm_step: null buffer");
+  if (!e || !actions || !obs || !rew || !done) return dm_fail(e, DM_EINVAL, "dm_step: null buffer");
   DmLaunch P;
   fill_launch(e, P, DMK_MODE_STEP);
   P.actions = actions; P.obs = obs; P.rew = rew; P.done = done; P.terms = terms; P.reason = reason; P.terminal_obs = terminal_obs;
   P.cost = e->dCost;
-  if (e->cfg.lpt_schedule) {
-    HIPCHK(e, hipSetDevice(e->cfg.device));
-    hipLaunchKernelGGL(dm_schedule_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, e->dCost, e->dOrder, e->N);
-    P.env_ids = e->dOrder;
-  }
-  return launch(e, P, e->N, stream);
+  const int rc = schedule(e, P, stream);
+  return rc != DM_OK ? rc : launch(e, P, e->N, stream);
 }
 
 extern "C" int dm_step_active(DmHandle e, const float *actions, const int32_t *env_ids, int nslots, float *obs, float *rew,
                               uint8_t *done, float *terms, int32_t *reason, void *stream) {
-  if (!e || !actions || !env_ids || !obs || !rew || !done || nslots < 1 || nslots > e->N) return fail(e, DM_EINVAL, "dm_step_active: bad argument");
+  if (!e || !actions || !env_ids || !obs || !rew || !done || nslots < 1 || nslots > e->N) return dm_fail(e, DM_EINVAL, "dm_step_active: bad argument");
   DmLaunch P;
   fill_launch(e, P, DMK_MODE_STEP);
   P.actions = actions; P.obs = obs; P.rew = rew; P.done = done; P.terms = terms; P.reason = reason;
@@ -421,22 +253,18 @@ extern "C" int dm_step_active(DmHandle e, const float *actions, const int32_t *e
 }
 
 extern "C" int dm_physics_step(DmHandle e, const float *actions, void *stream) {
-  if (!e || !actions) return fail(e, DM_EINVAL, "dm_physics_step: null buffer");
+  if (!e || !actions) return dm_fail(e, DM_EINVAL, "dm_physics_step: null buffer");
   DmLaunch P;
   fill_launch(e, P, DMK_MODE_PHYSICS);
   P.actions = actions;
   P.auto_reset = 0;
-  if (e->cfg.lpt_schedule) {   // same launch order as a dm_step from this state: the work estimates of the last dm_step
-    HIPCHK(e, hipSetDevice(e->cfg.device));
-    hipLaunchKernelGGL(dm_schedule_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, e->dCost, e->dOrder, e->N);
-    P.env_ids = e->dOrder;
-  }
-  return launch(e, P, e->N, stream);
+  const int rc = schedule(e, P, stream);   // same launch order as a dm_step from this state
+  return rc != DM_OK ? rc : launch(e, P, e->N, stream);
 }
 
 extern "C" int dm_step_forced(DmHandle e, const float *qpos, const float *qvel, float *obs, float *rew, uint8_t *done,
                               float *terms, int32_t *reason, void *stream) {
-  if (!e || !qpos || !qvel || !obs || !rew || !done) return fail(e, DM_EINVAL, "dm_step_forced: null buffer");
+  if (!e || !qpos || !qvel || !obs || !rew || !done) return dm_fail(e, DM_EINVAL, "dm_step_forced: null buffer");
   DmLaunch P;
   fill_launch(e, P, DMK_MODE_FORCED);
   P.in_qpos = qpos; P.in_qvel = qvel; P.obs = obs; P.rew = rew; P.done = done; P.terms = terms; P.reason = reason;
@@ -446,7 +274,7 @@ extern "C" int dm_step_forced(DmHandle e, const float *qpos, const float *qvel, 
 
 extern "C" int dm_set_state(DmHandle e, const int32_t *env_ids, int n, const float *qpos, const float *qvel,
                             const float *warm, const float *ctrl, int run_forward, void *stream) {
-  if (!e || !qpos || !qvel || n < 1 || n > e->N) return fail(e, DM_EINVAL, "dm_set_state: bad argument");
+  if (!e || !qpos || !qvel || n < 1 || n > e->N) return dm_fail(e, DM_EINVAL, "dm_set_state: bad argument");
   DmLaunch P;
   fill_launch(e, P, DMK_MODE_SETSTATE);
   P.env_ids = env_ids; P.in_qpos = qpos; P.in_qvel = qvel; P.in_warm = warm; P.in_ctrl = ctrl; P.run_forward = run_forward;
@@ -454,7 +282,7 @@ extern "C" int dm_set_state(DmHandle e, const int32_t *env_ids, int n, const flo
 }
 
 extern "C" int dm_forward(DmHandle e, const int32_t *env_ids, int n, void *stream) {
-  if (!e || n < 1 || n > e->N) return fail(e, DM_EINVAL, "dm_forward: bad argument");
+  if (!e || n < 1 || n > e->N) return dm_fail(e, DM_EINVAL, "dm_forward: bad argument");
   DmLaunch P;
   fill_launch(e, P, DMK_MODE_SETSTATE);
   P.env_ids = env_ids; P.run_forward = 1;     // in_qpos == null: state is kept
@@ -463,27 +291,24 @@ extern "C" int dm_forward(DmHandle e, const int32_t *env_ids, int n, void *strea
 
 extern "C" int dm_get_state(DmHandle e, const int32_t *env_ids, int n, float *qpos, float *qvel, float *warm,
                             float *ctrl, void *stream) {
-  if (!e || n < 1 || n > e->N) return fail(e, DM_EINVAL, "dm_get_state: bad argument");
-  HIPCHK(e, hipSetDevice(e->cfg.device));
-  hipLaunchKernelGGL(dm_get_state_kernel, dim3(n), dim3(64), 0, (hipStream_t)stream, e->dState, env_ids, n, e->N, qpos, qvel, warm, ctrl);
-  HIPCHK(e, hipGetLastError());
+  if (!e || n < 1 || n > e->N) return dm_fail(e, DM_EINVAL, "dm_get_state: bad argument");
+  DM_DEVICE(e);
+  DM_LAUNCH(e, dm_get_state_kernel, dim3(n), dim3(64), 0, (hipStream_t)stream, e->dState, env_ids, n, e->N, qpos, qvel, warm, ctrl);
   return DM_OK;
 }
 
 extern "C" int dm_get_counters(DmHandle e, int32_t *idx, int32_t *len, float *rew, void *stream) {
   if (!e) return DM_EINVAL;
-  HIPCHK(e, hipSetDevice(e->cfg.device));
-  hipLaunchKernelGGL(dm_counters_kernel, dim3((e->N + 255) / 256), dim3(256), 0, (hipStream_t)stream, e->dState, e->N, idx, len, rew,
+  DM_DEVICE(e);
+  DM_LAUNCH(e, dm_counters_kernel, dim3((e->N + 255) / 256), dim3(256), 0, (hipStream_t)stream, e->dState, e->N, idx, len, rew,
                      (const int32_t *)nullptr, (const int32_t *)nullptr);
-  HIPCHK(e, hipGetLastError());
   return DM_OK;
 }
 extern "C" int dm_set_counters(DmHandle e, const int32_t *idx, const int32_t *len, void *stream) {
   if (!e) return DM_EINVAL;
-  HIPCHK(e, hipSetDevice(e->cfg.device));
-  hipLaunchKernelGGL(dm_counters_kernel, dim3((e->N + 255) / 256), dim3(256), 0, (hipStream_t)stream, e->dState, e->N,
+  DM_DEVICE(e);
+  DM_LAUNCH(e, dm_counters_kernel, dim3((e->N + 255) / 256), dim3(256), 0, (hipStream_t)stream, e->dState, e->N,
                      (int32_t *)nullptr, (int32_t *)nullptr, (float *)nullptr, idx, len);
-  HIPCHK(e, hipGetLastError());
   return DM_OK;
 }
 
@@ -514,7 +339,7 @@ __global__ void dm_schedule_kernel(const int32_t *cost, int32_t *order, int n) {
 
 extern "C" int dm_get_work(DmHandle e, int32_t *work_out, void *stream) {
   if (!e || !work_out) return DM_EINVAL;
-  HIPCHK(e, hipSetDevice(e->cfg.device));
+  DM_DEVICE(e);
   HIPCHK(e, hipMemcpyAsync(work_out, e->dCost, e->N * sizeof(int32_t), hipMemcpyDeviceToDevice, (hipStream_t)stream));
   return DM_OK;
 }
@@ -533,10 +358,9 @@ extern "C" int dm_set_debug(DmHandle e, float *buf) {
 
 extern "C" int dm_fill_random_actions(DmHandle e, float *actions, uint32_t step_index, void *stream) {
   if (!e || !actions) return DM_EINVAL;
-  HIPCHK(e, hipSetDevice(e->cfg.device));
+  DM_DEVICE(e);
   int n = e->N * DM_NU;
-  hipLaunchKernelGGL(dm_fill_actions_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, actions, e->N, e->cfg.seed, step_index);
-  HIPCHK(e, hipGetLastError());
+  DM_LAUNCH(e, dm_fill_actions_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, actions, e->N, e->cfg.seed, step_index);
   return DM_OK;
 }
 
@@ -551,6 +375,7 @@ extern "C" int dm_enable_timing(DmHandle e, int enable) {
 extern "C" int dm_last_step_ms(DmHandle e, float *ms) {
   if (!e || !ms || !e->timing || e->nrec < 1) return DM_EINVAL;
   const int i = (int)((e->nrec - 1) % DmEngine::NEV);
+  DM_DEVICE(e);
   HIPCHK(e, hipEventSynchronize(e->ev1[i]));
   HIPCHK(e, hipEventElapsedTime(ms, e->ev0[i], e->ev1[i]));
   return DM_OK;
@@ -558,6 +383,7 @@ extern "C" int dm_last_step_ms(DmHandle e, float *ms) {
 extern "C" int dm_mean_step_ms(DmHandle e, float *ms, int32_t *count) {
   if (!e || !ms || !e->timing || e->nrec < 1) return DM_EINVAL;
   const long n = e->nrec < DmEngine::NEV ? e->nrec : DmEngine::NEV;
+  DM_DEVICE(e);
   double acc = 0;
   for (long k = 0; k < n; k++) {
     const int i = (int)((e->nrec - 1 - k) % DmEngine::NEV);

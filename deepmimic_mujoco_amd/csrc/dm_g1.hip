@@ -34,11 +34,7 @@
 #include <string>
 #include <vector>
 
-#define DM_OK 0
-#define DM_EINVAL (-22)
-#define DM_ENOMEM (-12)
-#define DM_EHIP (-5)
-#define DM_ENODEV (-19)
+#include "dm_g1_tables_host.h"   // g1_check_model, g1_build_tables, g1_build_meshes, g1_pack_clip; dm_host.h: DmHost, HIPCHK, DM_DEVICE, DM_LAUNCH
 
 namespace g1 {
 
@@ -430,10 +426,10 @@ extern "C" __global__ void g1_scatter_int_kernel(float *state, int N, int off, i
 }  // namespace g1
 
 // ------------------------------------------------------------------------------------------ host side (C-ABI)
-struct DmG1Engine {
+struct DmG1Engine : DmHost {
   DmG1Config cfg;
   int N = 0;
-  std::string err;
+  g1::Dev T;                     // host copy of *dT: dmg1_load_clip packs the clip rows with it
   g1::Dev *dT = nullptr;
   double *dMesh = nullptr, *dClus = nullptr;
   int32_t *dOidx = nullptr;
@@ -455,18 +451,8 @@ struct DmG1Engine {
   float *dPqCon = nullptr, *dSepc2 = nullptr;
 };
 
-static int g1_fail(DmG1Engine *e, int code, const char *msg) {
-  if (e) e->err = msg;
-  return code;
-}
 // why the last dmg1_create failed: there is no handle to carry the text, so dmg1_last_error(NULL) returns it
 static std::string g1_create_err = "null handle";
-static int g1_create_fail(DmG1Engine *e, int code, const char *msg) {
-  g1_create_err = msg;
-  fprintf(stderr, "dmg1_create: %s\n", msg);
-  delete e;
-  return code;
-}
 
 extern "C" void dmg1_default_config(DmG1Config *c) {
   memset(c, 0, sizeof *c);
@@ -478,342 +464,89 @@ extern "C" void dmg1_default_config(DmG1Config *c) {
 }
 extern "C" size_t dmg1_model_sizeof(void) { return sizeof(DmModelG1); }
 
-static void g1_build_tables(const DmModelG1 &m, g1::Dev &T) {
-  using namespace g1;
-  memset(&T, 0, sizeof T);
-  T.timestep = (float)m.timestep; T.tolerance = (float)m.tolerance;
-  T.pgs_scale = (float)(1.0 / (m.meaninertia * (double)NV));
-  const double tc = fmax(m.solref[0], 2 * m.timestep), dr = m.solref[1], dmax = m.solimp[1];   // refsafe
-  T.K = (float)(1.0 / fmax(1e-15, dmax * dmax * tc * tc * dr * dr));
-  T.B = (float)(2.0 / fmax(1e-15, dmax * tc));
-  for (int i = 0; i < 5; i++) T.solimp[i] = (float)m.solimp[i];
-  for (int i = 0; i < 3; i++) T.gravity[i] = (float)m.gravity[i];
-  double mt = 0;
-  for (int b = 1; b < NB; b++) mt += m.body_mass[b];
-  T.total_mass_inv = (float)(1.0 / mt);
-  T.low_z = (float)m.low_z; T.action_scale = (float)m.action_scale;
-  T.iterations = m.iterations; T.npair = m.npair;
-  T.torso_body = m.torso_body; T.floor_geom = m.floor_geom; T.rfoot_geom = m.rfoot_geom; T.lfoot_geom = m.lfoot_geom;
-  for (int i = 0; i < 4; i++) T.ee_geom[i] = m.ee_geom[i];
-  for (int i = 0; i < 8; i++) T.extra_geom[i] = m.extra_geom[i];
-  for (int i = 0; i < NREW; i++) { T.rew_q[i] = m.rew_qposadr[i]; T.rew_v[i] = m.rew_dofadr[i]; T.rew_j[i] = m.rew_jnt[i]; }
-  for (int i = 0; i < NQ; i++) { T.qpos0[i] = (float)m.qpos0[i]; T.qpos0_d[i] = m.qpos0[i]; }
-  T.timestep_d = m.timestep;
-  int maxd = 0;
-  for (int b = 0; b < NB; b++) {
-    T.b_parent[b] = m.body_parent[b]; T.b_depth[b] = m.body_depth[b]; T.b_dof[b] = m.body_dofadr[b];
-    if (m.body_depth[b] > maxd) maxd = m.body_depth[b];
-    for (int i = 0; i < 3; i++) { T.b_pos[b][i] = (float)m.body_pos[b][i]; T.b_ipos[b][i] = (float)m.body_ipos[b][i]; }
-    for (int i = 0; i < 4; i++) { T.b_quat[b][i] = (float)m.body_quat[b][i]; T.b_quat_d[b][i] = m.body_quat[b][i]; }
-    for (int i = 0; i < 3; i++) T.b_pos_d[b][i] = m.body_pos[b][i];
-    for (int i = 0; i < 6; i++) T.b_inertia[b][i] = (float)m.body_inertia[b][i];
-    T.b_mass[b] = (float)m.body_mass[b]; T.b_invw[b] = (float)m.body_invweight0[b][0];
+// Everything dmg1_create puts on the device.  On failure e->err says why and the caller deletes e, which frees what was made.
+static int g1_init(DmG1Engine *e, const DmModelG1 &m) {
+  const DmG1Config &cfg = e->cfg;
+  if (g1_check_model(m, e->err) != DM_OK) return DM_EINVAL;
+  if (cfg.integrator != DM_CFG_INT_MODEL && cfg.integrator != DM_CFG_INT_EULER && cfg.integrator != DM_CFG_INT_RK4)
+    return dm_fail(e, DM_EINVAL, "DmG1Config.integrator must be DM_CFG_INT_MODEL, DM_CFG_INT_EULER or DM_CFG_INT_RK4");
+  e->integrator = cfg.integrator == DM_CFG_INT_EULER ? DM_INT_EULER : cfg.integrator == DM_CFG_INT_RK4 ? DM_INT_RK4 : m.integrator;
+  g1_build_tables(m, e->T);
+  std::vector<double> verts, clus;
+  std::vector<int32_t> oidx;
+  if (g1_build_meshes(m, e->T, verts, oidx, clus) != 0) return dm_fail(e, DM_EINVAL, "a hull has more vertex clusters than 64 * g1::NCH");
+  DM_DEVICE(e);
+  HIPCHK(e, e->alloc(&e->dT, 1));
+  HIPCHK(e, e->upload(e->dT, &e->T, 1));
+  HIPCHK(e, e->alloc(&e->dMesh, verts.size()));
+  HIPCHK(e, e->upload(e->dMesh, verts.data(), verts.size()));
+  HIPCHK(e, e->alloc(&e->dOidx, oidx.size()));
+  HIPCHK(e, e->upload(e->dOidx, oidx.data(), oidx.size()));
+  HIPCHK(e, e->alloc(&e->dClus, clus.size()));
+  HIPCHK(e, e->upload(e->dClus, clus.data(), clus.size()));
+  const size_t N = (size_t)e->N;
+  std::vector<float> init(N * g1::STATE, 0.f);
+  for (size_t i = 0; i < N; i++)
+    for (int k = 0; k < g1::NQ; k++) init[i * g1::STATE + g1::S_QPOS + k] = (float)m.qpos0[k];
+  HIPCHK(e, e->alloc(&e->dState, init.size()));
+  HIPCHK(e, e->upload(e->dState, init.data(), init.size()));
+  HIPCHK(e, e->alloc(&e->dJT, N * 44 * g1::MAXROW));
+  HIPCHK(e, e->alloc(&e->dBT, N * 44 * g1::MAXROW));
+  HIPCHK(e, e->alloc(&e->dAR, N * g1::MAXROW * g1::MAXROW));
+  HIPCHK(e, e->alloc(&e->dRowsE, N * 5 * g1::MAXROW));
+  HIPCHK(e, e->alloc(&e->dSepc, N * (4 * g1::SEPC + 4)));
+  HIPCHK(e, e->fill(e->dSepc, 0xFF, N * (4 * g1::SEPC + 4) * sizeof(float)));   // pair id -1 everywhere
+  HIPCHK(e, e->alloc(&e->dOrder, N));
+  HIPCHK(e, e->alloc(&e->dCost, N));
+  HIPCHK(e, e->fill(e->dCost, 0, N * sizeof(int32_t)));
+  if (e->integrator == DM_INT_EULER) HIPCHK(e, e->alloc(&e->dQM, N * g1::QM_STRIDE));
+  e->split = cfg.pipeline == 2 || (cfg.pipeline == 0 && e->N >= 512);
+#ifdef G1_PROFILE
+  if (const char *pl = getenv("DMG1_PIPELINE")) e->split = atoi(pl) == 2;
+#endif
+  if (e->split) {   // ~135 KB per env: 0.55 GB at 4 096 envs
+    const size_t NP = N * g1::PAIRCAP;
+    HIPCHK(e, e->alloc(&e->dWs, N * g1::WS_BYTES));
+    HIPCHK(e, e->alloc(&e->dPqGeo, NP * 36));
+    HIPCHK(e, e->alloc(&e->dPqPair, NP));
+    HIPCHK(e, e->alloc(&e->dPqCnt, NP));
+    HIPCHK(e, e->alloc(&e->dPqCon, NP * 8 * 16));
+    HIPCHK(e, e->alloc(&e->dTick, 2 * NP));
+    HIPCHK(e, e->alloc(&e->dQctr, 8 * 4));
+    HIPCHK(e, e->alloc(&e->dSepc2, N * 1024 * 4));
+    HIPCHK(e, e->fill(e->dSepc2, 0xFF, N * 1024 * 4 * sizeof(float)));   // pair id -1 everywhere
   }
-  T.maxdepth = maxd;
-  for (int b = 1; b < NB; b++)
-    for (int a = b; a > 0; a = m.body_parent[a]) T.b_desc[a] |= 1ull << b;
-  for (int k = 0; k < NV; k++) {
-    T.d_body[k] = m.dof_body[k]; T.d_madr[k] = m.dof_Madr[k]; T.d_act[k] = -1;
-    int n = 0;
-    for (int j = m.dof_parent[k]; j >= 0; j = m.dof_parent[j]) T.d_anc[k][n++] = (uint8_t)j;
-    T.d_nanc[k] = n;
-    const int j = m.dof_jnt[k];
-    for (int i = 0; i < 3; i++) { T.d_axis[k][i] = (float)m.jnt_axis[j][i]; T.d_axis_d[k][i] = m.jnt_axis[j][i]; }
-    T.d_arm[k] = (float)m.dof_armature[k]; T.d_damp[k] = (float)m.dof_damping[k]; T.d_invw[k] = (float)m.dof_invweight0[k];
-    T.d_floss[k] = (float)m.dof_frictionloss[k];
-    T.d_lo[k] = (float)m.jnt_range[j][0]; T.d_hi[k] = (float)m.jnt_range[j][1];
-    if (!m.jnt_limited[j]) { T.d_lo[k] = -1e30f; T.d_hi[k] = 1e30f; }
-  }
-  for (int b = 1; b < NB; b++) {   // dofs that move body b: dofs of b and of its ancestors
-    for (int a = b; a > 0; a = m.body_parent[a])
-      for (int k = m.body_dofadr[a]; k < m.body_dofadr[a] + m.body_dofnum[a]; k++) T.b_chain[b] |= 1ull << k;
-  }
-  for (int a = 0; a < NU; a++) {
-    const int k = m.act_dof[a];
-    T.d_act[k] = a; T.d_clo[k] = (float)m.act_ctrlrange[a][0]; T.d_chi[k] = (float)m.act_ctrlrange[a][1];
-  }
-  for (int g = 0; g < NG; g++) {
-    T.g_body[g] = m.geom_body[g]; T.g_type[g] = m.geom_type[g]; T.g_mesh[g] = m.geom_mesh[g];
-    for (int i = 0; i < 3; i++) {
-      T.g_pos[g][i] = (float)m.geom_pos[g][i]; T.g_size[g][i] = (float)m.geom_size[g][i];
-      T.g_pos_d[g][i] = m.geom_pos[g][i]; T.g_size_d[g][i] = m.geom_size[g][i];
-    }
-    const double *q = m.geom_quat[g];
-    const double w = q[0], x = q[1], y = q[2], z = q[3];
-    const double M[9] = {w * w + x * x - y * y - z * z, 2 * (x * y - w * z), 2 * (x * z + w * y),
-                         2 * (x * y + w * z), w * w - x * x + y * y - z * z, 2 * (y * z - w * x),
-                         2 * (x * z - w * y), 2 * (y * z + w * x), w * w - x * x - y * y + z * z};
-    for (int i = 0; i < 9; i++) { T.g_mat[g][i] = (float)M[i]; T.g_mat_d[g][i] = M[i]; }
-    T.g_rbound[g] = (float)m.geom_rbound[g]; T.g_mu[g] = (float)m.geom_friction[g][0];
-    const double *zs = m.geom_size[g];
-    double lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
-    if (m.geom_type[g] == DM_GEOM_SPHERE) { for (int i = 0; i < 3; i++) { lo[i] = -zs[0]; hi[i] = zs[0]; } }
-    else if (m.geom_type[g] == DM_GEOM_CYLINDER) { lo[0] = lo[1] = -zs[0]; hi[0] = hi[1] = zs[0]; lo[2] = -zs[1]; hi[2] = zs[1]; }
-    else if (m.geom_type[g] == DM_GEOM_BOX) { for (int i = 0; i < 3; i++) { lo[i] = -zs[i]; hi[i] = zs[i]; } }
-    else if (m.geom_type[g] == DM_GEOM_MESH && m.geom_mesh[g] >= 0) {
-      const int me = m.geom_mesh[g];
-      for (int i = 0; i < 3; i++) { lo[i] = 1e30; hi[i] = -1e30; }
-      for (int v = m.mesh_vertadr[me]; v < m.mesh_vertadr[me] + m.mesh_vertnum[me]; v++)
-        for (int i = 0; i < 3; i++) { lo[i] = fmin(lo[i], m.mesh_vert[v][i]); hi[i] = fmax(hi[i], m.mesh_vert[v][i]); }
-    }
-    for (int i = 0; i < 3; i++) { T.g_bc[g][i] = (float)(0.5 * (lo[i] + hi[i])); T.g_bh[g][i] = (float)(0.5 * (hi[i] - lo[i]) * 1.00001 + 1e-6); }
-  }
-  for (int g = 0; g < 96; g++) T.g_ci[g] = -1;
-  int nci = 0;
-  for (int p = 0; p < m.npair; p++) {
-    T.p_g1[p] = (int16_t)m.pair_geom1[p]; T.p_g2[p] = (int16_t)m.pair_geom2[p];
-    for (int q = 0; q < 2; q++) { const int g = q ? m.pair_geom2[p] : m.pair_geom1[p]; if (T.g_ci[g] < 0 && nci < NCG) T.g_ci[g] = nci++; }
-  }
-  for (int i = 0; i < DM_NMESH; i++)
-    for (int k = 0; k < 3; k++) T.m_center[i][k] = m.mesh_center[i][k];   // vertex / cluster ranges: g1_build_meshes
-  int p = 0;
-  for (int b = 0; b < 15 && p < 128; b++)   // pairs (a <= c), c-major: index p -> (a, c)
-    for (int a = 0; a <= b && p < 128; a++) { T.tri_a[p] = (uint8_t)a; T.tri_b[p] = (uint8_t)b; p++; }
-  for (int k = 0; k < NV; k++) {
-    const int n = T.d_nanc[k], np = n * (n + 1) / 2;
-    for (int l = 0; l < 64; l++) {
-      uint32_t w = 0;
-      for (int hf = 0; hf < 2; hf++) {
-        const int q = l + 64 * hf;
-        uint32_t t = 0;
-        if (q < np) { const int a = T.tri_a[q], c = T.tri_b[q]; t = (uint32_t)(T.d_madr[T.d_anc[k][a]] + (c - a)); }
-        w |= t << (16 * hf);
-      }
-      T.f_tgt[k][l] = w;
-    }
-  }
-}
-
-// Reorder every hull into compact clusters: a k-d partition along the longest extent, split so that the left side is a whole
-// number of 64-vertex leaves (every leaf but one per hull is full); a leaf occupies 64 vertex slots (unused slots carry the
-// invalid original index 0x7fffffff) and has two bounds: an enclosing sphere (centre shrunk from the mean of the vertices by
-// Badoiu-Clarkson steps) and a box about the same centre.
-static void g1_kd_split(const DmModelG1 &m, int a0, std::vector<int> &idx, int lo, int hi, std::vector<std::pair<int, int>> &leaves) {
-  if (hi - lo <= 64) { leaves.push_back({lo, hi}); return; }
-  double mn[3] = {1e30, 1e30, 1e30}, mx[3] = {-1e30, -1e30, -1e30};
-  for (int k = lo; k < hi; k++)
-    for (int i = 0; i < 3; i++) { mn[i] = fmin(mn[i], m.mesh_vert[a0 + idx[k]][i]); mx[i] = fmax(mx[i], m.mesh_vert[a0 + idx[k]][i]); }
-  int ax = 0;
-  for (int i = 1; i < 3; i++) if (mx[i] - mn[i] > mx[ax] - mn[ax]) ax = i;
-  const int half = (hi - lo) / 2, mid = lo + ((half + 63) / 64) * 64 < hi ? lo + ((half + 63) / 64) * 64 : (lo + hi) / 2;   // left side: full leaves
-  std::nth_element(idx.begin() + lo, idx.begin() + mid, idx.begin() + hi, [&](int p, int q) {
-    const double vp = m.mesh_vert[a0 + p][ax], vq = m.mesh_vert[a0 + q][ax];
-    return vp < vq || (vp == vq && p < q);
-  });
-  g1_kd_split(m, a0, idx, lo, mid, leaves);
-  g1_kd_split(m, a0, idx, mid, hi, leaves);
-}
-static int g1_build_meshes(const DmModelG1 &m, g1::Dev &T, std::vector<double> &verts, std::vector<int32_t> &oidx,
-                            std::vector<double> &clus) {
-  int vadr = 0, cadr = 0;
-  for (int me = 0; me < DM_NMESH; me++) {
-    const int n = m.mesh_vertnum[me], a0 = m.mesh_vertadr[me];
-    T.m_vadr[me] = vadr; T.m_cadr[me] = cadr; T.m_vnum[me] = 0; T.m_cnum[me] = 0;
-    if (n == 0) continue;
-    std::vector<int> idx(n);
-    for (int k = 0; k < n; k++) idx[k] = k;
-    std::vector<std::pair<int, int>> leaves;
-    g1_kd_split(m, a0, idx, 0, n, leaves);
-    for (auto &lf : leaves) {
-      double cc[3] = {0, 0, 0}, rad = 0;
-      const int cnt = lf.second - lf.first;
-      for (int k = lf.first; k < lf.second; k++) for (int i = 0; i < 3; i++) cc[i] += m.mesh_vert[a0 + idx[k]][i];
-      for (int i = 0; i < 3; i++) cc[i] /= cnt;
-      auto radius_at = [&](const double *c3) {
-        double r = 0;
-        for (int k = lf.first; k < lf.second; k++) {
-          double d2 = 0;
-          for (int i = 0; i < 3; i++) { const double df = m.mesh_vert[a0 + idx[k]][i] - c3[i]; d2 += df * df; }
-          r = fmax(r, sqrt(d2));
-        }
-        return r;
-      };
-      rad = radius_at(cc);
-      {   // a tighter enclosing sphere (Badoiu-Clarkson steps towards the farthest vertex): fewer clusters survive the bound test
-        double c2[3] = {cc[0], cc[1], cc[2]};
-        for (int it = 1; it <= 200; it++) {
-          int far = lf.first; double best = -1;
-          for (int k = lf.first; k < lf.second; k++) {
-            double d2 = 0;
-            for (int i = 0; i < 3; i++) { const double df = m.mesh_vert[a0 + idx[k]][i] - c2[i]; d2 += df * df; }
-            if (d2 > best) { best = d2; far = k; }
-          }
-          for (int i = 0; i < 3; i++) c2[i] += (m.mesh_vert[a0 + idx[far]][i] - c2[i]) / (it + 1);
-          const double r2 = radius_at(c2);
-          if (r2 < rad) { rad = r2; for (int i = 0; i < 3; i++) cc[i] = c2[i]; }
-        }
-      }
-      for (int k = lf.first; k < lf.second; k++) {
-        for (int i = 0; i < 3; i++) verts.push_back(m.mesh_vert[a0 + idx[k]][i]);
-        oidx.push_back(idx[k]);
-      }
-      for (int k = cnt; k < 64; k++) { verts.push_back(0); verts.push_back(0); verts.push_back(0); oidx.push_back(0x7fffffff); }
-      clus.push_back(cc[0]); clus.push_back(cc[1]); clus.push_back(cc[2]); clus.push_back(rad * (1 + 1e-9) + 1e-12);
-      double hx[3] = {0, 0, 0};
-      for (int k = lf.first; k < lf.second; k++)
-        for (int i = 0; i < 3; i++) hx[i] = fmax(hx[i], fabs(m.mesh_vert[a0 + idx[k]][i] - cc[i]));
-      for (int i = 0; i < 3; i++) clus.push_back(hx[i] * (1 + 1e-9) + 1e-12);
-      clus.push_back(0.0);
-    }
-    const int nclus = (int)leaves.size();
-    if (nclus > 64 * g1::NCH) return -1;
-    T.m_vnum[me] = nclus * 64; T.m_cnum[me] = nclus;
-    vadr += nclus * 64; cadr += nclus;
-  }
-  return 0;
-}
-
-static int g1_check_model(DmG1Engine *e, const DmModelG1 &m) {
-  using namespace g1;
-  if (m.nq != NQ || m.nv != NV || m.nu != NU || m.nbody != NB || m.ngeom != NG || m.njnt != NJ || m.nM != NM)
-    return g1_fail(e, DM_EINVAL, "model dimensions are not the Unitree G1's");
-  if (m.integrator != DM_INT_RK4 && m.integrator != DM_INT_EULER) return g1_fail(e, DM_EINVAL, "integrator must be RK4 or Euler");
-  if (m.npair < 0 || m.npair > 1024) return g1_fail(e, DM_EINVAL, "npair out of range");
-  if (m.jnt_type[0] != DM_JNT_FREE || m.jnt_body[0] != 1) return g1_fail(e, DM_EINVAL, "joint 0 must be the free root");
-  for (int b = 2; b < NB; b++)
-    if (m.body_jntnum[b] != 1 || m.body_dofadr[b] != b + 4 || m.body_jntadr[b] != b - 1 || m.body_depth[b] > 15)
-      return g1_fail(e, DM_EINVAL, "kernel assumes one hinge per body in body order");
-  for (int j = 0; j < NJ; j++)
-    for (int i = 0; i < 3; i++)
-      if (m.jnt_pos[j][i] != 0.0) return g1_fail(e, DM_EINVAL, "kernel assumes joint anchors at the body origin");
-  for (int k = 0; k < NV; k++) {
-    int n = 0;
-    for (int j = m.dof_parent[k]; j >= 0; j = m.dof_parent[j]) n++;
-    if (n > 14) return g1_fail(e, DM_EINVAL, "dof chain deeper than 14 ancestors");
-    if (m.dof_parent[k] != g1topo::PARENT[k] || m.dof_Madr[k] != g1topo::MADR[k])
-      return g1_fail(e, DM_EINVAL, "dof tree differs from the compiled-in topology (regenerate csrc/dm_g1_topology.h)");
-    if (k >= 6 && !(m.dof_frictionloss[k] > 0)) return g1_fail(e, DM_EINVAL, "kernel assumes friction loss on every hinge");
-  }
-  for (int a = 0; a < NU; a++)
-    if (m.act_gear[a] != 1.0) return g1_fail(e, DM_EINVAL, "kernel assumes motor gear 1");
-  {
-    int seen[DM_NGEOM] = {0}, nci = 0;
-    for (int p = 0; p < m.npair; p++) { seen[m.pair_geom1[p]] = 1; seen[m.pair_geom2[p]] = 1; }
-    for (int g = 0; g < NG; g++) nci += seen[g];
-    if (nci > NCG) return g1_fail(e, DM_EINVAL, "more colliding geoms than the kernel's LDS layout holds");
-  }
-  for (int g = 0; g < NG; g++) {
-    if (m.geom_margin[g] != 0.0) return g1_fail(e, DM_EINVAL, "kernel assumes zero geom margins (xml has none)");
-    if (m.geom_mesh[g] >= DM_NMESH) return g1_fail(e, DM_EINVAL, "mesh id out of range");
-  }
+  HIPCHK(e, e->event(&e->ev0));
+  HIPCHK(e, e->event(&e->ev1));
   return DM_OK;
 }
 
 extern "C" int dmg1_create(const void *model, size_t model_bytes, const DmG1Config *cfg, DmG1Handle *out) {
   if (!model || !cfg || !out || cfg->num_envs < 1) return DM_EINVAL;
   if (model_bytes != sizeof(DmModelG1)) { fprintf(stderr, "dmg1_create: model struct size %zu != %zu\n", model_bytes, sizeof(DmModelG1)); return DM_EINVAL; }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return DM_ENODEV;
-  const DmModelG1 &m = *(const DmModelG1 *)model;
+  if (!dm_have_device()) return DM_ENODEV;
   DmG1Engine *e = new DmG1Engine();
   e->cfg = *cfg;
+  e->device = cfg->device;
   e->N = cfg->num_envs;
-  int rc = g1_check_model(e, m);
-  if (rc != DM_OK) { const std::string why = e->err; return g1_create_fail(e, rc, why.c_str()); }
-  if (cfg->integrator != DM_CFG_INT_MODEL && cfg->integrator != DM_CFG_INT_EULER && cfg->integrator != DM_CFG_INT_RK4)
-    return g1_create_fail(e, DM_EINVAL, "DmG1Config.integrator must be DM_CFG_INT_MODEL, DM_CFG_INT_EULER or DM_CFG_INT_RK4");
-  e->integrator = cfg->integrator == DM_CFG_INT_EULER ? DM_INT_EULER : cfg->integrator == DM_CFG_INT_RK4 ? DM_INT_RK4 : m.integrator;
-  if (hipSetDevice(cfg->device) != hipSuccess) { delete e; return DM_ENODEV; }
-  g1::Dev *T = new g1::Dev();
-  g1_build_tables(m, *T);
-  std::vector<double> verts, clus;
-  std::vector<int32_t> oidx;
-  if (g1_build_meshes(m, *T, verts, oidx, clus) != 0) {
-    delete T; delete e; fprintf(stderr, "dmg1_create: a hull has more than %d vertex clusters\n", 64 * g1::NCH); return DM_EINVAL;
-  }
-  bool ok = hipMalloc(&e->dT, sizeof(g1::Dev)) == hipSuccess;
-  if (ok) hipMemcpy(e->dT, T, sizeof(g1::Dev), hipMemcpyHostToDevice);
-  delete T;
-  ok = ok && hipMalloc(&e->dMesh, verts.size() * sizeof(double)) == hipSuccess;
-  ok = ok && hipMalloc(&e->dOidx, oidx.size() * sizeof(int32_t)) == hipSuccess;
-  ok = ok && hipMalloc(&e->dClus, clus.size() * sizeof(double)) == hipSuccess;
-  if (ok) {
-    hipMemcpy(e->dMesh, verts.data(), verts.size() * sizeof(double), hipMemcpyHostToDevice);
-    hipMemcpy(e->dOidx, oidx.data(), oidx.size() * sizeof(int32_t), hipMemcpyHostToDevice);
-    hipMemcpy(e->dClus, clus.data(), clus.size() * sizeof(double), hipMemcpyHostToDevice);
-  }
-  const size_t N = (size_t)e->N;
-  ok = ok && hipMalloc(&e->dState, N * g1::STATE * sizeof(float)) == hipSuccess;
-  ok = ok && hipMalloc(&e->dJT, N * 44 * g1::MAXROW * sizeof(float)) == hipSuccess;
-  ok = ok && hipMalloc(&e->dBT, N * 44 * g1::MAXROW * sizeof(float)) == hipSuccess;
-  ok = ok && hipMalloc(&e->dAR, N * g1::MAXROW * g1::MAXROW * sizeof(float)) == hipSuccess;
-  ok = ok && hipMalloc(&e->dRowsE, N * 5 * g1::MAXROW * sizeof(float)) == hipSuccess;
-  ok = ok && hipMalloc(&e->dSepc, N * (4 * g1::SEPC + 4) * sizeof(float)) == hipSuccess;
-  if (ok) hipMemset(e->dSepc, 0xFF, N * (4 * g1::SEPC + 4) * sizeof(float));   // pair id -1 everywhere
-  ok = ok && hipMalloc(&e->dOrder, N * sizeof(int32_t)) == hipSuccess && hipMalloc(&e->dCost, N * sizeof(int32_t)) == hipSuccess;
-  if (ok) hipMemset(e->dCost, 0, N * sizeof(int32_t));
-  if (e->integrator == DM_INT_EULER) ok = ok && hipMalloc(&e->dQM, N * g1::QM_STRIDE * sizeof(float)) == hipSuccess;
-  e->split = cfg->pipeline == 2 || (cfg->pipeline == 0 && e->N >= 512);
-#ifdef G1_PROFILE
-  if (const char *pl = getenv("DMG1_PIPELINE")) e->split = atoi(pl) == 2;
-#endif
-  if (e->split) {   // ~135 KB per env: 0.55 GB at 4 096 envs
-    const size_t NP = N * g1::PAIRCAP;
-    ok = ok && hipMalloc(&e->dWs, N * g1::WS_BYTES) == hipSuccess;
-    ok = ok && hipMalloc(&e->dPqGeo, NP * 36 * sizeof(double)) == hipSuccess;
-    ok = ok && hipMalloc(&e->dPqPair, NP * sizeof(int32_t)) == hipSuccess && hipMalloc(&e->dPqCnt, NP * sizeof(int32_t)) == hipSuccess;
-    ok = ok && hipMalloc(&e->dPqCon, NP * 8 * 16 * sizeof(float)) == hipSuccess;
-    ok = ok && hipMalloc(&e->dTick, 2 * NP * sizeof(int32_t)) == hipSuccess && hipMalloc(&e->dQctr, 8 * 4 * sizeof(int32_t)) == hipSuccess;
-    ok = ok && hipMalloc(&e->dSepc2, N * 1024 * 4 * sizeof(float)) == hipSuccess;
-    if (ok) hipMemset(e->dSepc2, 0xFF, N * 1024 * 4 * sizeof(float));   // pair id -1 everywhere
-  }
-  if (!ok) { dmg1_destroy(e); return DM_ENOMEM; }
-  std::vector<float> init(N * g1::STATE, 0.f);
-  for (size_t i = 0; i < N; i++)
-    for (int k = 0; k < g1::NQ; k++) init[i * g1::STATE + g1::S_QPOS + k] = (float)m.qpos0[k];
-  hipMemcpy(e->dState, init.data(), init.size() * sizeof(float), hipMemcpyHostToDevice);
-  hipEventCreate(&e->ev0); hipEventCreate(&e->ev1);
+  const int rc = g1_init(e, *(const DmModelG1 *)model);
+  if (rc != DM_OK) { g1_create_err = e->err; fprintf(stderr, "dmg1_create: %s\n", e->err.c_str()); delete e; return rc; }
   *out = e;
   return DM_OK;
 }
 
-extern "C" int dmg1_destroy(DmG1Handle e) {
-  if (!e) return DM_EINVAL;
-  hipFree(e->dWs); hipFree(e->dPqGeo); hipFree(e->dPqPair); hipFree(e->dPqCnt); hipFree(e->dPqCon); hipFree(e->dTick); hipFree(e->dQctr); hipFree(e->dSepc2);
-  hipFree(e->dQM);
-  hipFree(e->dT); hipFree(e->dMesh); hipFree(e->dOidx); hipFree(e->dClus); hipFree(e->dState); hipFree(e->dJT); hipFree(e->dBT); hipFree(e->dAR); hipFree(e->dRowsE); hipFree(e->dSepc); hipFree(e->dOrder); hipFree(e->dCost);
-  for (int c = 0; c < DMG1_MAX_CLIPS; c++) { hipFree(e->dRows[c]); hipFree(e->dReset[c]); hipFree(e->dCom[c]); }
-  if (e->ev0) hipEventDestroy(e->ev0);
-  if (e->ev1) hipEventDestroy(e->ev1);
-  delete e;
-  return DM_OK;
-}
+extern "C" int dmg1_destroy(DmG1Handle e) { return dm_destroy_engine(e); }
 extern "C" const char *dmg1_last_error(DmG1Handle e) { return e ? e->err.c_str() : g1_create_err.c_str(); }
 
 extern "C" int dmg1_load_clip(DmG1Handle e, int clip_id, int L, const double *q, const double *v, const double *bx, const double *gx, int flags) {
   using namespace g1;
   if (!e || L < 1 || !q || !v || !bx || !gx || clip_id < 0 || clip_id >= DMG1_MAX_CLIPS) return DM_EINVAL;
-  g1::Dev *T = new g1::Dev();
-  hipMemcpy(T, e->dT, sizeof(g1::Dev), hipMemcpyDeviceToHost);
+  DM_DEVICE(e);
   std::vector<float> rows((size_t)L * CLIP_ROW, 0.f), reset((size_t)L * RESET_ROW, 0.f), com((size_t)L * COM_ROW, 0.f);
-  double mt = 0;
-  for (int b = 0; b < NB; b++) mt += T->b_mass[b];
-  for (int f = 0; f < L; f++) {
-    float *r = &rows[(size_t)f * CLIP_ROW];
-    for (int i = 0; i < NREW; i++) { r[CR_QPOS + i] = (float)q[(size_t)f * NQ + T->rew_q[i]]; r[CR_QVEL + i] = (float)v[(size_t)f * NV + T->rew_v[i]]; }
-    for (int i = 0; i < 4; i++) r[CR_ROOTQ + i] = (float)q[(size_t)f * NQ + 3 + i];
-    r[CR_ROOTV] = (float)v[(size_t)f * NV]; r[CR_ROOTV + 1] = (float)v[(size_t)f * NV + 1];
-    for (int e4 = 0; e4 < 4; e4++)
-      for (int i = 0; i < 3; i++) r[CR_EE + 3 * e4 + i] = (float)gx[((size_t)f * NG + T->ee_geom[e4]) * 3 + i];
-    for (int i = 0; i < NQ; i++) reset[(size_t)f * RESET_ROW + RR_QPOS + i] = (float)q[(size_t)f * NQ + i];
-    for (int i = 0; i < NV; i++) reset[(size_t)f * RESET_ROW + RR_QVEL + i] = (float)v[(size_t)f * NV + i];
-    for (int i = 0; i < 3; i++) {
-      double s = 0;
-      for (int b = 0; b < NB; b++) s += (double)T->b_mass[b] * bx[((size_t)f * NB + b) * 3 + i];
-      com[(size_t)f * COM_ROW + i] = (float)(s / mt);
-    }
-  }
-  delete T;
+  g1_pack_clip(e->T, L, q, v, bx, gx, rows.data(), reset.data(), com.data());
   const int c = clip_id;
-  if (hipSetDevice(e->cfg.device) != hipSuccess) return g1_fail(e, DM_EHIP, "hipSetDevice failed");
-  hipFree(e->dRows[c]); hipFree(e->dReset[c]); hipFree(e->dCom[c]);
-  e->dRows[c] = e->dReset[c] = e->dCom[c] = nullptr;
-  if (hipMalloc(&e->dRows[c], rows.size() * 4) != hipSuccess || hipMalloc(&e->dReset[c], reset.size() * 4) != hipSuccess ||
-      hipMalloc(&e->dCom[c], com.size() * 4) != hipSuccess)
-    return g1_fail(e, DM_ENOMEM, "clip tables");
-  hipMemcpy(e->dRows[c], rows.data(), rows.size() * 4, hipMemcpyHostToDevice);
-  hipMemcpy(e->dReset[c], reset.data(), reset.size() * 4, hipMemcpyHostToDevice);
-  hipMemcpy(e->dCom[c], com.data(), com.size() * 4, hipMemcpyHostToDevice);
+  e->L[c] = 0;   // an empty slot if the reload fails
+  HIPCHK(e, e->reload({{&e->dRows[c], &rows}, {&e->dReset[c], &reset}, {&e->dCom[c], &com}}));
   e->L[c] = L; e->flags[c] = flags;
   return DM_OK;
 }
@@ -830,9 +563,8 @@ static int g1_launch(DmG1Engine *e, g1::Launch &P, void *stream, bool time_it, c
   P.debug = e->dDebug;
   P.qm = e->dQM;
   const bool euler = P.mode == g1::MODE_STEP && e->integrator == DM_INT_EULER;   // the other modes run one evaluation and integrate nothing
-  if (!e->L[0]) return g1_fail(e, DM_EINVAL, "no clip loaded (dmg1_load_clip clip 0 first)");
-  if (e->cfg.task && (e->L[1] < 1 || e->L[2] < 2)) return g1_fail(e, DM_EINVAL, "combined task needs clips 0, 1, 2 = walk, run, getup");
-  if (hipSetDevice(e->cfg.device) != hipSuccess) return g1_fail(e, DM_EHIP, "hipSetDevice failed");
+  if (const char *why = dm_clips_missing(e->L, e->cfg.task != 0, true)) return dm_fail(e, DM_EINVAL, why);
+  DM_DEVICE(e);
   bool lpt = true;
   P.skip = e->skip;
 #ifdef G1_PROFILE   // phase switches of the diagnostic build only: the shipped library never reads the environment on a launch
@@ -840,11 +572,11 @@ static int g1_launch(DmG1Engine *e, g1::Launch &P, void *stream, bool time_it, c
   lpt = !getenv("DMG1_NO_LPT");
 #endif
   hipStream_t s = (hipStream_t)stream;
-  if (time_it) hipEventRecord(e->ev0, s);
+  if (time_it) HIPCHK(e, hipEventRecord(e->ev0, s));
   if (slots) P.order = slots;
   if (P.mode == g1::MODE_STEP && e->N >= 512 && lpt) {   // longest-first order from the previous step's costs
     if (!slots || e->active_lpt) {
-      hipLaunchKernelGGL(g1::g1_schedule_kernel, dim3(1), dim3(1024), 0, s, e->dCost, slots, nl, e->N, e->dOrder);
+      DM_LAUNCH(e, g1::g1_schedule_kernel, dim3(1), dim3(1024), 0, s, e->dCost, slots, nl, e->N, e->dOrder);
       P.order = e->dOrder;
     }
   }
@@ -854,7 +586,7 @@ static int g1_launch(DmG1Engine *e, g1::Launch &P, void *stream, bool time_it, c
     // under Euler 3 around 2.  The counters of the rounds that do not run stay at the zeros of the memset (dmg1_queue_counters).
     P.ws = e->dWs; P.pq_geo = e->dPqGeo; P.pq_pair = e->dPqPair; P.pq_cnt = e->dPqCnt; P.pq_con = e->dPqCon; P.tick = e->dTick;
     P.qctr = e->dQctr; P.sepc2 = e->dSepc2;
-    hipMemsetAsync(e->dQctr, 0, 8 * 4 * sizeof(int32_t), s);
+    HIPCHK(e, hipMemsetAsync(e->dQctr, 0, 8 * 4 * sizeof(int32_t), s));
     g1::PairLaunch Q;
     memset(&Q, 0, sizeof Q);
     Q.T = e->dT; Q.mesh_vert = e->dMesh; Q.mesh_oidx = e->dOidx; Q.mesh_clus = e->dClus; Q.pq_geo = e->dPqGeo; Q.pq_pair = e->dPqPair;
@@ -863,24 +595,24 @@ static int g1_launch(DmG1Engine *e, g1::Launch &P, void *stream, bool time_it, c
     const int rounds = euler ? 3 : 6;
     for (int r = 0; r < rounds; r++) {
       P.round = r;
-      if (euler) hipLaunchKernelGGL(g1::g1_env_euler_kernel, dim3(nl), dim3(64), 0, s, P);
-      else hipLaunchKernelGGL(g1::g1_env_kernel, dim3(nl), dim3(64), 0, s, P);
+      if (euler) DM_LAUNCH(e, g1::g1_env_euler_kernel, dim3(nl), dim3(64), 0, s, P);
+      else DM_LAUNCH(e, g1::g1_env_kernel, dim3(nl), dim3(64), 0, s, P);
       if (r < rounds - 1) {
         Q.qctr = e->dQctr + 4 * r;
-        hipLaunchKernelGGL(g1::g1_pair_kernel, dim3(pair_waves), dim3(64), 0, s, Q);
+        DM_LAUNCH(e, g1::g1_pair_kernel, dim3(pair_waves), dim3(64), 0, s, Q);
       }
     }
   } else if (euler) {
-    hipLaunchKernelGGL(g1::g1_step_euler_kernel, dim3(nl), dim3(64), 0, s, P);
+    DM_LAUNCH(e, g1::g1_step_euler_kernel, dim3(nl), dim3(64), 0, s, P);
   } else {
-    hipLaunchKernelGGL(g1::g1_step_kernel, dim3(nl), dim3(64), 0, s, P);
+    DM_LAUNCH(e, g1::g1_step_kernel, dim3(nl), dim3(64), 0, s, P);
   }
-  if (time_it) { hipEventRecord(e->ev1, s); e->timed = true; }
-  return hipGetLastError() == hipSuccess ? DM_OK : g1_fail(e, DM_EHIP, "kernel launch failed");
+  if (time_it) { HIPCHK(e, hipEventRecord(e->ev1, s)); e->timed = true; }
+  return DM_OK;
 }
 
 extern "C" int dmg1_reset(DmG1Handle e, const uint8_t *mask, const int32_t *idx_init, float *obs_out, void *stream) {
-  if (!e || !e->L[0]) return e ? g1_fail(e, DM_EINVAL, "no clip loaded") : DM_EINVAL;
+  if (!e) return DM_EINVAL;
   g1::Launch P;
   memset(&P, 0, sizeof P);
   P.mode = g1::MODE_RESET; P.mask = mask; P.idx_init = idx_init; P.obs = obs_out;
@@ -889,7 +621,6 @@ extern "C" int dmg1_reset(DmG1Handle e, const uint8_t *mask, const int32_t *idx_
 extern "C" int dmg1_step(DmG1Handle e, const float *actions, float *obs, float *rew, uint8_t *done, float *terms, int32_t *reason,
                          float *terminal_obs, void *stream) {
   if (!e || !actions) return DM_EINVAL;
-  if (!e->L[0]) return g1_fail(e, DM_EINVAL, "no clip loaded");
   g1::Launch P;
   memset(&P, 0, sizeof P);
   P.mode = g1::MODE_STEP; P.actions = actions; P.obs = obs; P.rew = rew; P.done = done; P.terms = terms; P.reason = reason;
@@ -899,8 +630,7 @@ extern "C" int dmg1_step(DmG1Handle e, const float *actions, float *obs, float *
 extern "C" int dmg1_step_active(DmG1Handle e, const float *actions, const int32_t *env_ids, int nslots, float *obs, float *rew,
                                 uint8_t *done, float *terms, int32_t *reason, void *stream) {
   if (!e) return DM_EINVAL;
-  if (!actions || !env_ids || !obs || !rew || !done || nslots < 1 || nslots > e->N) return g1_fail(e, DM_EINVAL, "dmg1_step_active: bad argument");
-  if (!e->L[0]) return g1_fail(e, DM_EINVAL, "no clip loaded");
+  if (!actions || !env_ids || !obs || !rew || !done || nslots < 1 || nslots > e->N) return dm_fail(e, DM_EINVAL, "dmg1_step_active: bad argument");
   g1::Launch P;
   memset(&P, 0, sizeof P);
   P.mode = g1::MODE_STEP; P.actions = actions; P.obs = obs; P.rew = rew; P.done = done; P.terms = terms; P.reason = reason;
@@ -914,7 +644,6 @@ extern "C" int dmg1_set_active_schedule(DmG1Handle e, int on) {
 extern "C" int dmg1_step_forced(DmG1Handle e, const float *qpos, const float *qvel, float *obs, float *rew, uint8_t *done,
                                 float *terms, int32_t *reason, void *stream) {
   if (!e || !qpos || !qvel) return DM_EINVAL;
-  if (!e->L[0]) return g1_fail(e, DM_EINVAL, "no clip loaded");
   g1::Launch P;
   memset(&P, 0, sizeof P);
   P.mode = g1::MODE_FORCED; P.in_qpos = qpos; P.in_qvel = qvel; P.obs = obs; P.rew = rew; P.done = done; P.terms = terms; P.reason = reason;
@@ -927,37 +656,47 @@ extern "C" int dmg1_set_state(DmG1Handle e, const float *qpos, const float *qvel
   P.mode = g1::MODE_SETSTATE; P.in_qpos = qpos; P.in_qvel = qvel; P.in_warm = warm; P.run_forward = run_forward;
   return g1_launch(e, P, stream, false);
 }
-static void g1_gather(DmG1Engine *e, int off, int n, float *out, void *stream) {
+// out = null: nothing to do
+static int g1_gather(DmG1Engine *e, int off, int n, float *out, void *stream) {
+  if (!out) return DM_OK;
   const int tot = e->N * n;
-  hipLaunchKernelGGL(g1::g1_gather_kernel, dim3((tot + 255) / 256), dim3(256), 0, (hipStream_t)stream, e->dState, e->N, off, n, g1::STATE, out);
+  DM_DEVICE(e);
+  DM_LAUNCH(e, g1::g1_gather_kernel, dim3((tot + 255) / 256), dim3(256), 0, (hipStream_t)stream, e->dState, e->N, off, n, g1::STATE, out);
+  return DM_OK;
+}
+static int g1_scatter(DmG1Engine *e, int off, const int32_t *in, void *stream) {
+  if (!in) return DM_OK;
+  DM_DEVICE(e);
+  DM_LAUNCH(e, g1::g1_scatter_int_kernel, dim3((e->N + 255) / 256), dim3(256), 0, (hipStream_t)stream, e->dState, e->N, off, g1::STATE, in);
+  return DM_OK;
 }
 extern "C" int dmg1_get_state(DmG1Handle e, float *qpos, float *qvel, float *warm, void *stream) {
   if (!e) return DM_EINVAL;
-  if (qpos) g1_gather(e, g1::S_QPOS, g1::NQ, qpos, stream);
-  if (qvel) g1_gather(e, g1::S_QVEL, g1::NV, qvel, stream);
-  if (warm) g1_gather(e, g1::S_WARM, g1::NV, warm, stream);
-  return DM_OK;
+  int rc = g1_gather(e, g1::S_QPOS, g1::NQ, qpos, stream);
+  if (rc == DM_OK) rc = g1_gather(e, g1::S_QVEL, g1::NV, qvel, stream);
+  if (rc == DM_OK) rc = g1_gather(e, g1::S_WARM, g1::NV, warm, stream);
+  return rc;
 }
 extern "C" int dmg1_get_counters(DmG1Handle e, int32_t *idx, int32_t *eplen, float *eprew, void *stream) {
   if (!e) return DM_EINVAL;
-  if (idx) g1_gather(e, g1::S_IDX, 1, (float *)idx, stream);
-  if (eplen) g1_gather(e, g1::S_EPLEN, 1, (float *)eplen, stream);
-  if (eprew) g1_gather(e, g1::S_EPREW, 1, eprew, stream);
-  return DM_OK;
+  int rc = g1_gather(e, g1::S_IDX, 1, (float *)idx, stream);
+  if (rc == DM_OK) rc = g1_gather(e, g1::S_EPLEN, 1, (float *)eplen, stream);
+  if (rc == DM_OK) rc = g1_gather(e, g1::S_EPREW, 1, eprew, stream);
+  return rc;
 }
 extern "C" int dmg1_set_counters(DmG1Handle e, const int32_t *idx, const int32_t *eplen, void *stream) {
   if (!e) return DM_EINVAL;
-  const int nb = (e->N + 255) / 256;
-  if (idx) hipLaunchKernelGGL(g1::g1_scatter_int_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, e->dState, e->N, g1::S_IDX, g1::STATE, idx);
-  if (eplen) hipLaunchKernelGGL(g1::g1_scatter_int_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, e->dState, e->N, g1::S_EPLEN, g1::STATE, eplen);
-  return DM_OK;
+  const int rc = g1_scatter(e, g1::S_IDX, idx, stream);
+  return rc != DM_OK ? rc : g1_scatter(e, g1::S_EPLEN, eplen, stream);
 }
 extern "C" int dmg1_queue_counters(DmG1Handle e, int32_t *host_out24) {
   if (!e || !host_out24) return DM_EINVAL;
   memset(host_out24, 0, 24 * sizeof(int32_t));
   if (!e->split) return DM_OK;
-  if (hipSetDevice(e->cfg.device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return DM_EHIP;
-  return hipMemcpy(host_out24, e->dQctr, 24 * sizeof(int32_t), hipMemcpyDeviceToHost) == hipSuccess ? DM_OK : DM_EHIP;
+  DM_DEVICE(e);
+  HIPCHK(e, hipDeviceSynchronize());
+  HIPCHK(e, hipMemcpy(host_out24, e->dQctr, 24 * sizeof(int32_t), hipMemcpyDeviceToHost));
+  return DM_OK;
 }
 extern "C" int dmg1_set_seed(DmG1Handle e, uint64_t seed) {
   if (!e) return DM_EINVAL;
@@ -967,13 +706,11 @@ extern "C" int dmg1_set_seed(DmG1Handle e, uint64_t seed) {
 extern "C" int dmg1_obs_dim(DmG1Handle e) { return e ? (e->cfg.task ? DMG1_NOBS_COMBINED : DMG1_NOBS) : DM_EINVAL; }
 extern "C" int dmg1_get_motion(DmG1Handle e, int32_t *motion, void *stream) {
   if (!e || !motion) return DM_EINVAL;
-  g1_gather(e, g1::S_MOTION, 1, (float *)motion, stream);
-  return DM_OK;
+  return g1_gather(e, g1::S_MOTION, 1, (float *)motion, stream);
 }
 extern "C" int dmg1_set_motion(DmG1Handle e, const int32_t *motion, void *stream) {
   if (!e || !motion) return DM_EINVAL;
-  hipLaunchKernelGGL(g1::g1_scatter_int_kernel, dim3((e->N + 255) / 256), dim3(256), 0, (hipStream_t)stream, e->dState, e->N, g1::S_MOTION, g1::STATE, motion);
-  return DM_OK;
+  return g1_scatter(e, g1::S_MOTION, motion, stream);
 }
 extern "C" int dmg1_set_env_clips(DmG1Handle e, const int32_t *clip_ids, void *stream) { return dmg1_set_motion(e, clip_ids, stream); }
 extern "C" int dmg1_get_env_clips(DmG1Handle e, int32_t *clip_ids, void *stream) { return dmg1_get_motion(e, clip_ids, stream); }
@@ -990,23 +727,27 @@ extern "C" int dmg1_set_null_cache(DmG1Handle e, int on) {
 extern "C" int dmg1_sep_cache_entries(DmG1Handle e, int32_t *host_out2) {
   if (!e || !host_out2) return DM_EINVAL;
   host_out2[0] = host_out2[1] = 0;
-  if (hipSetDevice(e->cfg.device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return DM_EHIP;
+  DM_DEVICE(e);
+  HIPCHK(e, hipDeviceSynchronize());
   const size_t per_env = 4 * g1::SEPC + 4;
   std::vector<int32_t> h((size_t)e->N * per_env);
-  if (hipMemcpy(h.data(), e->dSepc, h.size() * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess) return DM_EHIP;
+  HIPCHK(e, hipMemcpy(h.data(), e->dSepc, h.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
   for (int env = 0; env < e->N; env++)
     for (int k = 0; k < g1::SEPC; k++) host_out2[0] += h[env * per_env + 4 * k] >= 0;
   if (e->split && e->dSepc2) {
     h.resize((size_t)e->N * 1024 * 4);
-    if (hipMemcpy(h.data(), e->dSepc2, h.size() * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess) return DM_EHIP;
+    HIPCHK(e, hipMemcpy(h.data(), e->dSepc2, h.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
     for (size_t k = 0; k < (size_t)e->N * 1024; k++) host_out2[1] += h[4 * k] >= 0;
   }
   return DM_OK;
 }
+static int g1_kernel_ms(DmG1Engine *e, float *ms) {
+  DM_DEVICE(e);
+  HIPCHK(e, hipEventSynchronize(e->ev1));
+  HIPCHK(e, hipEventElapsedTime(ms, e->ev0, e->ev1));
+  return DM_OK;
+}
 extern "C" float dmg1_last_kernel_ms(DmG1Handle e) {
-  if (!e || !e->timed) return -1.f;
   float ms = -1.f;
-  if (hipEventSynchronize(e->ev1) != hipSuccess) return -1.f;
-  if (hipEventElapsedTime(&ms, e->ev0, e->ev1) != hipSuccess) return -1.f;
-  return ms;
+  return e && e->timed && g1_kernel_ms(e, &ms) == DM_OK ? ms : -1.f;
 }

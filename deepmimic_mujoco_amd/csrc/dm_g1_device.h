@@ -16,6 +16,7 @@ namespace g1 {
 constexpr int NQ = 44, NV = 43, NU = 37, NB = 39, NG = 94, NJ = 38, NM = 434, NACT = 23, NOBS = 85, NREW = 23;
 constexpr int MAXCON = DMG1_MAXCON, MAXROW = DMG1_MAXROW, MAXANC = 16, MAXSURV = 384, NCG = 48;   // NCG: geoms that collide (47)
 constexpr int PAIRCAP = 128;    // split pipeline: surviving pairs per env and evaluation that the pair queue holds (monolithic: MAXSURV)
+constexpr int NCH = 2;          // cluster chunks of 64 per hull: hulls of up to 128 clusters (g1_build_meshes checks)
 constexpr int QM_STRIDE = 448;  // Euler: floats per env of the parked mass matrix (NM entries, rows of 64 B)
 constexpr int STATE = 176;   // floats per env in the HBM state row
 constexpr int S_QPOS = 0, S_QVEL = 44, S_WARM = 87, S_CTRL = 130, S_IDX = 167, S_EPLEN = 168, S_EPREW = 169, S_RCNT = 170, S_MOTION = 171;

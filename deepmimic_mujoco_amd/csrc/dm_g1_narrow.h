@@ -18,7 +18,6 @@ struct Geo {
 };
 
 // ---- support mapping of a hull (see mesh_support_pair below)
-constexpr int NCH = 2;            // cluster chunks of 64 per hull: hulls of up to 128 clusters (checked at create)
 // Support ties (oracle/dm_convex.h "ties"): MPR queries a hull along its portal normal, in which two hull vertices tie EXACTLY by
 // construction at every edge-edge / face-vertex contact; "first strict maximum" is then decided by the last bit of two dot
 // products and ends in a different contact normal.  Rule (both sides): values within SUP_TIE of the maximum are tied, the
