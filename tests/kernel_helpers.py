@@ -1,7 +1,8 @@
 """What the GPU tests of the learner kernels share: library / pointer / stream accessors, NaN-guarded output buffers, offset input
-views, the measured-against-bound print, the out8 check and the Python restatement of the kernels' counter-based draws
+views, the measured-against-bound print, the element-by-element `within` check, the out8 check and the Python restatement of the kernels' counter-based draws
 (csrc/dm_rng.h).  A plain module: importing it touches no GPU."""
 import ctypes as C
+import functools
 
 import numpy as np
 import torch
@@ -60,6 +61,35 @@ def note(what, err, tol, width=34):
     """The measured error against its bound (printed with pytest -s: the numbers the docstrings quote)."""
     print("measured %-*s %10.3g   bound %10.3g   margin %8.1fx" % (width, what, err, tol, tol / max(err, 1e-30)))
     return err
+
+
+MISSES = []
+
+
+def checked(test):
+    """`within` records a miss and goes on, so one run shows every quantity that is out of bounds; the test fails at its end."""
+    @functools.wraps(test)
+    def run(*args, **kw):
+        MISSES.clear()
+        test(*args, **kw)
+        assert not MISSES, MISSES
+    return run
+
+
+def within(what, got, val, bnd):
+    """Every element of `got` within its bound of the fp64 value; prints the worst error / bound (a NaN or an error against a zero
+    bound is a miss)."""
+    g = got.detach().cpu().numpy().astype(np.float64) if isinstance(got, torch.Tensor) else np.asarray(got, np.float64)
+    val = np.asarray(val, np.float64)
+    g = g.reshape(val.shape)
+    err = np.abs(g - val)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ratio = np.where(err == 0, 0.0, err / np.broadcast_to(np.asarray(bnd, np.float64), val.shape))
+    worst = float(np.max(ratio)) if ratio.size else 0.0
+    note(what, worst, 1.0, width=46)
+    if not worst <= 1.0:
+        MISSES.append((what, round(worst, 2), "element %d, %d of %d out" % (int(np.argmax(ratio)), int((~(ratio <= 1.0)).sum()), ratio.size)))
+    return worst
 
 
 def check_out8(out8, ref8, ratio64, clip, B, width=34):

@@ -405,7 +405,9 @@ def test_physics_step_is_sim_step_alone(model, clips):
 
 
 def test_hip_linear_wgrad_matches_torch():
-    """dm_linear_wgrad (MFMA split-K) against torch's weight / bias gradients for every layer shape of both nets."""
+    """dm_linear_wgrad (MFMA split-K) against torch's weight / bias gradients for every layer shape of both nets: the smoke check
+    at the workload's shapes.  The per-path checks (every split, tile edge and refusal, against fp64 with derived bounds) live in
+    tests/test_ppo_layer_kernels_gpu.py."""
     import torch
     from deepmimic_mujoco_amd.ppo import HipLinear
     dev = torch.device("cuda", 0)
@@ -428,7 +430,9 @@ def test_hip_linear_wgrad_matches_torch():
 
 def test_fused_tanh_layer_kernels_match_torch():
     """dm_linear_tanh / dm_tanh_linear_wgrad / dm_tanh_bwd_colsum (the activation fused around the GEMMs of the wide trunks)
-    against torch, for every observation width of the reference's envs and ragged sizes."""
+    against torch, for every observation width of the reference's envs and one ragged size: the smoke check at the workload's
+    shapes.  The per-path checks (every staging path, NT instantiation, tail loop and lt_tanh branch, against fp64 with derived
+    bounds) live in tests/test_ppo_layer_kernels_gpu.py."""
     import ctypes as C
     import torch
     from deepmimic_mujoco_amd import _lib

@@ -16,7 +16,7 @@ import pytest
 import torch
 
 import sac_kernels_ref64 as ref
-from kernel_helpers import DEV, guard_ok, guarded, note
+from kernel_helpers import DEV, checked, guard_ok, guarded, within
 
 pytestmark = pytest.mark.gpu
 
@@ -68,35 +68,6 @@ def same_bits(a, b):
 
 def untouched(t):
     return bool(torch.isnan(t).all())
-
-
-MISSES = []
-
-
-def checked(test):
-    """`within` records a miss and goes on, so one run shows every quantity that is out of bounds; the test fails at its end."""
-    @functools.wraps(test)
-    def run(*args, **kw):
-        MISSES.clear()
-        test(*args, **kw)
-        assert not MISSES, MISSES
-    return run
-
-
-def within(what, got, val, bnd):
-    """Every element of `got` within its bound of the fp64 value; prints the worst error / bound (a NaN or an error against a zero
-    bound is a miss)."""
-    g = host(got).astype(np.float64) if isinstance(got, torch.Tensor) else np.asarray(got, np.float64)
-    val = np.asarray(val, np.float64)
-    g = g.reshape(val.shape)
-    err = np.abs(g - val)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        ratio = np.where(err == 0, 0.0, err / np.broadcast_to(np.asarray(bnd, np.float64), val.shape))
-    worst = float(np.max(ratio)) if ratio.size else 0.0
-    note(what, worst, 1.0, width=46)
-    if not worst <= 1.0:
-        MISSES.append((what, round(worst, 2), "element %d, %d of %d out" % (int(np.argmax(ratio)), int((~(ratio <= 1.0)).sum()), ratio.size)))
-    return worst
 
 
 # ---------------------------------------------------------------------------------------------------------------- head forward
