@@ -37,6 +37,8 @@ EXPORTS = ["dm_default_config", "dm_create", "dm_destroy", "dm_last_error", "dm_
            "dm_step_active", "dm_eval_advance"]
 # include/deepmimic_render.h (csrc/dm_render.hip); EXPORTS above is the list of include/deepmimic_hip.h alone
 RENDER_EXPORTS = ["dm_render_create", "dm_render_destroy", "dm_render_last_error", "dm_render_kinematics", "dm_render_cast", "dm_render"]
+# include/deepmimic_trace.h (csrc/dm_trace.hip): the episode debug log, debug_log.FlightRecorder
+TRACE_EXPORTS = ["dm_trace_record", "dm_trace_mark", "dm_trace_last_error"]
 
 
 class DmConfig(C.Structure):
@@ -91,6 +93,14 @@ class DmPpoWideStep(DmPpoStepHead):
 
 class DmPpoWide3Step(DmPpoWideStep):
     """include/deepmimic_hip.h: DmPpoWide3Step — DmPpoWideStep's layout; every bf16 scratch array holds two planes (hi, lo)"""
+
+
+class DmTraceBufs(C.Structure):
+    """include/deepmimic_trace.h: DmTraceBufs"""
+    _fields_ = [("N", C.c_int32), ("K", C.c_int32), ("C", C.c_int32), ("nq", C.c_int32), ("nv", C.c_int32), ("na", C.c_int32),
+                ("W", C.c_int32), ("device", C.c_int32),
+                ("ring", C.c_void_p), ("head", C.c_void_p), ("cap", C.c_void_p), ("cap_meta", C.c_void_p), ("cap_count", C.c_void_p),
+                ("trig", C.c_void_p)]
 
 
 # floats of the state2 buffer of dm_flat_adam_*: {scratch, step count, DM_ADAM_PARTIALS partial sums} (include/deepmimic_hip.h)
@@ -193,6 +203,10 @@ def load_library():
     L.dm_render_kinematics.argtypes = [vp, vp, vp, i32, vp, vp, vp]
     L.dm_render_cast.argtypes = [vp, vp, vp, i32, vp, i32, i32, vp, vp, vp, vp]
     L.dm_render.argtypes = [vp, vp, vp, i32, vp, i32, i32, vp, vp, vp, vp, vp]
+    L.dm_trace_record.argtypes = [C.POINTER(DmTraceBufs)] + [vp] * 8 + [i32, C.c_uint32, vp]
+    L.dm_trace_mark.argtypes = [C.POINTER(DmTraceBufs)] + [vp] * 4 + [i32, vp]
+    L.dm_trace_last_error.argtypes = []
+    L.dm_trace_last_error.restype = C.c_char_p
     for name in EXPORTS:
         if name not in ("dm_default_config", "dm_last_error"):
             getattr(L, name).restype = C.c_longlong if name in ("dm_policy_packed_floats", "dm_ppo_mlp_workspace_floats", "dm_ppo_wide_packed_elems", "dm_ppo_wide3_packed_elems", "dm_rollout_finish_workspace_bytes") else C.c_int
@@ -271,23 +285,45 @@ class EngineBase:
         forward evaluation and the warm start is put back: looking at an env is not physics."""
         if self._debug is None:
             self.enable_debug()
-        self._refresh_derived()
+        rec, self._recorder = self._recorder, None      # the refresh goes through set_state: not an event of the episode
+        try:
+            self._refresh_derived()
+        finally:
+            self._recorder = rec
         return self._debug[env, :3 * self.NBODY].double().cpu().numpy().reshape(self.NBODY, 3)
 
-    # ---- hot path
+    # ---- hot path.  ``_recorder``: a debug_log.FlightRecorder attached to this engine, or None.  With one attached every step is
+    # followed by ``record`` and every state set from outside by ``mark``; without one the calls below are the engine's alone.
+    _recorder = None
+
+    def _reason_of(self, out):
+        """``out``'s reason tensor; the recorder's own when it needs one and the caller asked for none."""
+        r = out.get("reason")
+        return self._recorder.reason if (r is None and self._recorder is not None) else r
+
     def reset(self, obs, idx_init=None, mask=None):
         self._call("reset", mask, idx_init, obs)
+        if self._recorder is not None:
+            self._recorder.mark_reset(mask)
 
     def step(self, actions, out):
-        self._call("step", actions, out["obs"], out["rew"], out["done"], out.get("terms"), out.get("reason"), out.get("terminal_obs"))
+        reason = self._reason_of(out)
+        self._call("step", actions, out["obs"], out["rew"], out["done"], out.get("terms"), reason, out.get("terminal_obs"))
+        if self._recorder is not None:
+            self._recorder.record(actions, out, reason=reason)
 
     def step_forced(self, qpos, qvel, out):
         self._call("step_forced", qpos, qvel, out["obs"], out["rew"], out["done"], out.get("terms"), out.get("reason"))
+        if self._recorder is not None:
+            self._recorder.mark()
 
     def step_active(self, actions, env_ids, nslots, out):
         """``dm_step_active`` / ``dmg1_step_active``: the envs listed in ``env_ids[:nslots]`` (int32 device tensor, entries < 0
         skipped) take one step without auto-reset; ``actions`` and the rows of ``out`` stay indexed by env."""
-        self._call("step_active", actions, env_ids, int(nslots), out["obs"], out["rew"], out["done"], out.get("terms"), out.get("reason"))
+        reason = self._reason_of(out)
+        self._call("step_active", actions, env_ids, int(nslots), out["obs"], out["rew"], out["done"], out.get("terms"), reason)
+        if self._recorder is not None:
+            self._recorder.record(actions, out, env_ids=env_ids, nslots=int(nslots), reason=reason)
 
     def get_counters(self):
         """(idx_curr int32[N], episode_length int32[N], episode_reward float32[N])"""
@@ -357,6 +393,8 @@ class HipEngine(EngineBase):
 
     def set_state(self, qpos, qvel, warm=None, ctrl=None, env_ids=None, run_forward=False):
         self._call("set_state", env_ids, qpos.shape[0], qpos, qvel, warm, ctrl, 1 if run_forward else 0)
+        if self._recorder is not None:
+            self._recorder.mark(env_ids=env_ids, nslots=qpos.shape[0])
 
     def forward(self, env_ids=None, n=None):
         """sim.forward(): re-evaluate the derived quantities at the stored state."""

@@ -253,6 +253,8 @@ class G1HipEngine(EngineBase):
     def set_state(self, qpos, qvel, warm=None, run_forward=True):
         assert self._rows(qpos, qvel)
         self._call("set_state", qpos, qvel, warm, int(run_forward))
+        if self._recorder is not None:
+            self._recorder.mark()
 
     def get_state(self):
         q, v, w = self._zeros(NQ), self._zeros(NV), self._zeros(NV)

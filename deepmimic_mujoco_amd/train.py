@@ -58,6 +58,11 @@ def build_parser():
                          "the launches on either robot (compact=\"all\"); 0 = off")
     ap.add_argument("--renderer", default="stick", choices=["stick", "raycast"],
                     help="frames of the eval dashboard: host-side stick figure, or ray-cast on the device (raycast.py)")
+    ap.add_argument("--debug-log", default="", metavar="DIR",
+                    help="keep the reference's episode_debug_log on the device (debug_log.py): the last --debug-log-steps steps of every env; "
+                         "after each rollout the rings of envs whose step ended with a sim error or an out-of-bounds observation are "
+                         "written to DIR as deepmimic_episode_<time>_env<i>.json")
+    ap.add_argument("--debug-log-steps", type=int, default=64, help="--debug-log: steps kept per env")
     ap.add_argument("--run-name", default="run")
     ap.add_argument("--eval-dir", default="~/deep_mimic")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
@@ -115,6 +120,9 @@ def main(argv=None):
     else:
         env = HipDeepMimicVecEnv(args.envs, motion=motions if len(motions) > 1 else motions[0], device=local_rank,
                                  seed=1234 + 7919 * rank, sub_batches=sb, integrator=args.integrator)
+    # before the first rollout: a captured rollout graph holds the recorder's launches
+    dlog = env.enable_debug_log(steps=args.debug_log_steps) if args.debug_log else None
+    dlog_dir = os.path.expanduser(args.debug_log) if world == 1 else os.path.join(os.path.expanduser(args.debug_log), "rank%d" % rank)
     if args.algo == "sac":
         return _train_sac(args, env, motions, local_rank)
     ppo = PPO(env, net_arch=tuple(int(x) for x in args.arch.split(",")), n_steps=args.horizon,
@@ -137,6 +145,8 @@ def main(argv=None):
 
     def _cb(p):
         hist.append(dict(p.stats, timesteps=p.num_timesteps * world))
+        if dlog is not None:
+            dlog.dump(dlog_dir)
         if dash is not None:
             dash(p)
         return True
@@ -170,7 +180,8 @@ def main(argv=None):
                               "ep_rew_mean": hist[-1]["ep_rew_mean"], "ep_len_mean": hist[-1]["ep_len_mean"],
                               "explained_variance": hist[-1]["explained_variance"], "episodes": hist[-1]["episodes"],
                               "curve": [(h["timesteps"], h["ep_rew_mean"], h["ep_len_mean"]) for h in hist[::max(1, len(hist) // 200)]],
-                              **({"eval": final_eval} if final_eval is not None else {})}))
+                              **({"eval": final_eval} if final_eval is not None else {}),
+                              **({"debug_log": dict(zip(("captures", "triggers"), dlog.counts()), files=dlog.files)} if dlog is not None else {})}))
     if batch_env is not None:
         batch_env.close()
     env.close()
@@ -197,8 +208,12 @@ def _train_sac(args, env, motions, local_rank):
         dash = EvalDashboardCallback(eval_env, args.motion + "_" + args.run_name, every_n_global_steps=args.eval_every, out_root=args.eval_dir,
                                      batch_env=batch_env)
 
+    dlog = getattr(env, "debug_log", None)          # --debug-log: enable_debug_log() ran in main
+
     def _cb(m):
         hist.append(dict(m.stats))
+        if dlog is not None:
+            dlog.dump(os.path.expanduser(args.debug_log))
         if not args.json:
             print("steps %(total_timesteps)d  ep_rew_mean %(ep_rew_mean).3f  ep_len_mean %(ep_len_mean).1f  critic %(critic_loss).4f  "
                   "actor %(actor_loss).4f  ent_coef %(ent_coef).4f  fps %(fps).0f" % m.stats, flush=True)
@@ -225,7 +240,8 @@ def _train_sac(args, env, motions, local_rank):
                           "ep_rew_mean": last.get("ep_rew_mean"), "ep_len_mean": last.get("ep_len_mean"),
                           "critic_loss": last.get("critic_loss"), "actor_loss": last.get("actor_loss"), "ent_coef": last.get("ent_coef"),
                           "curve": [(h["total_timesteps"], h["ep_rew_mean"]) for h in hist[::max(1, len(hist) // 200)]],
-                          **({"eval": final_eval} if final_eval is not None else {})}))
+                          **({"eval": final_eval} if final_eval is not None else {}),
+                          **({"debug_log": dict(zip(("captures", "triggers"), dlog.counts()), files=dlog.files)} if dlog is not None else {})}))
     env.close()
 
 

@@ -295,6 +295,16 @@ class HipBatchEnv(_RayCastSurface, _SB3VecEnv):
         self.step_async(actions)
         return self.step_wait()
 
+    def enable_debug_log(self, steps=64, captures=16, reasons=("sim_error", "obs_out_of_bounds")):
+        """The reference's ``episode_debug_log`` for the batch (debug_log.py): from now on every engine keeps the last ``steps``
+        steps of each of its envs on the device and freezes up to ``captures`` copies (per engine, between two dumps) of the rings
+        of envs whose step ends with one of ``reasons``.  Returns the object whose ``dump(directory)`` writes them as
+        ``deepmimic_episode_<time>_env<i>.json`` and whose ``counts()`` is (captures, triggers).  Switch it on before a rollout
+        graph is captured."""
+        from .debug_log import BatchDebugLog
+        self.debug_log = BatchDebugLog(self, steps, captures, reasons)
+        return self.debug_log
+
     def close(self):
         if self._ray is not None:
             self._ray.close()
@@ -377,7 +387,26 @@ class HipSingleEnv(_RayCastSurface):
         else:
             self._eng.step(self._row(action), self._out)
         obs = self._out["obs"][0].double().cpu().numpy()
-        return obs, int(self._out["reason"][0].item()), bool(self._out["done"][0].item())
+        reason = int(self._out["reason"][0].item())
+        if self._debug_log is not None:
+            self._debug_log.on_step(reason)
+        return obs, reason, bool(self._out["done"][0].item())
+
+    # ---- src/deepmimic_env.py:299,457-476: episode_debug_log, off unless enable_debug_log() was called
+    _debug_log = None
+
+    def enable_debug_log(self):
+        """Keep the reference's ``episode_debug_log`` (debug_log.py): every step of the running episode on the device, cleared on
+        ``reset``; a step that ends with a sim error or an out-of-bounds observation writes ``/tmp/deepmimic_episode_<time>.json``
+        and prints the reference's message."""
+        from .debug_log import SingleDebugLog
+        self._debug_log = SingleDebugLog(self)
+        return self._debug_log
+
+    @property
+    def episode_debug_log(self):
+        """The reference-shaped dict of the running episode ({} before the first step, and without ``enable_debug_log``)."""
+        return {} if self._debug_log is None else self._debug_log.log()
 
     def _state(self):
         q, v = self._eng.get_state()[:2]
