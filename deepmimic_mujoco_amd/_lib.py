@@ -39,6 +39,8 @@ EXPORTS = ["dm_default_config", "dm_create", "dm_destroy", "dm_last_error", "dm_
 RENDER_EXPORTS = ["dm_render_create", "dm_render_destroy", "dm_render_last_error", "dm_render_kinematics", "dm_render_cast", "dm_render"]
 # include/deepmimic_trace.h (csrc/dm_trace.hip): the episode debug log, debug_log.FlightRecorder
 TRACE_EXPORTS = ["dm_trace_record", "dm_trace_mark", "dm_trace_last_error"]
+# include/deepmimic_vecnorm.h (csrc/dm_vecnorm.hip): SB3's VecNormalize, vec_normalize.HipVecNormalize
+VECNORM_EXPORTS = ["dm_vecnorm_scratch_bytes", "dm_vecnorm_step", "dm_vecnorm_reset", "dm_vecnorm_apply", "dm_vecnorm_last_error"]
 
 
 class DmConfig(C.Structure):
@@ -101,6 +103,14 @@ class DmTraceBufs(C.Structure):
                 ("W", C.c_int32), ("device", C.c_int32),
                 ("ring", C.c_void_p), ("head", C.c_void_p), ("cap", C.c_void_p), ("cap_meta", C.c_void_p), ("cap_count", C.c_void_p),
                 ("trig", C.c_void_p)]
+
+
+class DmVecNorm(C.Structure):
+    """include/deepmimic_vecnorm.h: DmVecNorm"""
+    _fields_ = [("N", C.c_int32), ("D", C.c_int32), ("device", C.c_int32), ("training", C.c_int32), ("norm_obs", C.c_int32),
+                ("norm_reward", C.c_int32), ("gamma", C.c_double), ("epsilon", C.c_double), ("clip_obs", C.c_double),
+                ("clip_reward", C.c_double), ("obs_mean", C.c_void_p), ("obs_var", C.c_void_p), ("obs_count", C.c_void_p),
+                ("ret_stats", C.c_void_p), ("returns", C.c_void_p), ("scratch", C.c_void_p), ("scratch_bytes", C.c_int64)]
 
 
 # floats of the state2 buffer of dm_flat_adam_*: {scratch, step count, DM_ADAM_PARTIALS partial sums} (include/deepmimic_hip.h)
@@ -207,6 +217,13 @@ def load_library():
     L.dm_trace_mark.argtypes = [C.POINTER(DmTraceBufs)] + [vp] * 4 + [i32, vp]
     L.dm_trace_last_error.argtypes = []
     L.dm_trace_last_error.restype = C.c_char_p
+    L.dm_vecnorm_scratch_bytes.argtypes = [i32, i32]
+    L.dm_vecnorm_scratch_bytes.restype = C.c_longlong
+    L.dm_vecnorm_step.argtypes = [C.POINTER(DmVecNorm)] + [vp] * 8
+    L.dm_vecnorm_reset.argtypes = [C.POINTER(DmVecNorm)] + [vp] * 3
+    L.dm_vecnorm_apply.argtypes = [C.POINTER(DmVecNorm), i32] + [vp] * 5
+    L.dm_vecnorm_last_error.argtypes = []
+    L.dm_vecnorm_last_error.restype = C.c_char_p
     for name in EXPORTS:
         if name not in ("dm_default_config", "dm_last_error"):
             getattr(L, name).restype = C.c_longlong if name in ("dm_policy_packed_floats", "dm_ppo_mlp_workspace_floats", "dm_ppo_wide_packed_elems", "dm_ppo_wide3_packed_elems", "dm_rollout_finish_workspace_bytes") else C.c_int

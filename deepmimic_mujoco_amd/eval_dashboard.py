@@ -13,8 +13,16 @@ import os
 import numpy as np
 
 
-def eval_dashboard_rollout(model, eval_env, n, run_name, log_wandb=False, out_root=None, max_steps=None, figures=True):
-    """Collect one episode with the deterministic policy and write the dashboard; returns (ep_len, ep_rew)."""
+def training_normalizer(model):
+    """The ``HipVecNormalize`` the model trains through, or None: evaluation then goes through its frozen statistics."""
+    from .vec_normalize import HipVecNormalize
+    env = getattr(model, "env", None)
+    return env if isinstance(env, HipVecNormalize) else None
+
+
+def eval_dashboard_rollout(model, eval_env, n, run_name, log_wandb=False, out_root=None, max_steps=None, figures=True, normalizer=None):
+    """Collect one episode with the deterministic policy and write the dashboard; returns (ep_len, ep_rew).  ``normalizer``: the
+    policy sees ``normalizer.normalize_obs(obs)``; rewards and the plotted observations stay raw."""
     import torch as th
     buffer = []
     obs = eval_env.reset()
@@ -22,8 +30,9 @@ def eval_dashboard_rollout(model, eval_env, n, run_name, log_wandb=False, out_ro
     while True:
         try:
             with th.no_grad():
-                action = model.predict(obs.reshape(1, -1), deterministic=True)[0].cpu().numpy()
-                val = float(model.policy.predict_values(th.as_tensor(obs.reshape(1, -1), dtype=th.float32, device=model.device))[0])
+                seen = obs.reshape(1, -1) if normalizer is None else normalizer.normalize_obs(obs.reshape(1, -1))
+                action = model.predict(seen, deterministic=True)[0].cpu().numpy()
+                val = float(model.policy.predict_values(th.as_tensor(seen, dtype=th.float32, device=model.device))[0])
         except Exception:   # the reference swallows predictor errors the same way (:41-42)
             action, val = np.zeros(eval_env.action_space.shape[0], np.float32), 0.0
         try:
@@ -134,7 +143,8 @@ class EvalDashboardCallback:
     def batch_evaluation(self, model, n):
         """One batched evaluation point -> its record (also appended to ``eval_batch.csv`` and ``batch_history``)."""
         from .evaluation import RECORD_FIELDS, evaluation_record
-        rec = evaluation_record(model, self.batch_env, n, start_frames=self.batch_start_frames, max_steps=self.max_steps)
+        rec = evaluation_record(model, self.batch_env, n, start_frames=self.batch_start_frames, max_steps=self.max_steps,
+                                normalizer=training_normalizer(model))
         video_dir = os.path.join(os.path.expanduser(self.out_root or "~/deep_mimic"), self.run_name + "_videos")
         os.makedirs(video_dir, exist_ok=True)
         path = os.path.join(video_dir, "eval_batch.csv")
@@ -151,7 +161,8 @@ class EvalDashboardCallback:
         if self.last_eval is None or n - self.last_eval >= self.every:
             self.last_eval = n
             self.history.append((n,) + eval_dashboard_rollout(model, self.eval_env, n, self.run_name, log_wandb=self.log_wandb,
-                                                              out_root=self.out_root, max_steps=self.max_steps, figures=self.figures))
+                                                              out_root=self.out_root, max_steps=self.max_steps, figures=self.figures,
+                                                              normalizer=training_normalizer(model)))
             if self.batch_env is not None:
                 self.batch_evaluation(model, n)
         return True

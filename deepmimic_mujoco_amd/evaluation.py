@@ -314,16 +314,25 @@ def resolve_frames(env, n_eval_episodes, start_frames):
     return n_eval_episodes, given[np.arange(n_eval_episodes) % given.size]
 
 
+def normalized_act_fn(act_fn, normalizer):
+    """``act_fn`` behind a ``vec_normalize.HipVecNormalize``'s frozen transform: the policy sees ``normalizer.normalize_obs(obs)``
+    (``dm_vecnorm_apply``, one launch for however many rows); the statistics are only read."""
+    if normalizer is None:
+        return act_fn
+    return lambda obs: act_fn(normalizer.normalize_obs(obs))
+
+
 def run_episodes(model, env, n_eval_episodes=None, start_frames="all", deterministic=True, max_steps=None, compact=True,
-                 sync_every=16):
+                 sync_every=16, normalizer=None):
     """The rounds behind ``evaluate_policy``: a list of ``EvalResult``, one per round of at most ``env.num_envs`` episodes.
     ``start_frames``: ``"all"`` (episode e from frame e mod L of a single-clip env's clip; ``n_eval_episodes`` defaults to L), an int array
     (episode e from ``start_frames[e mod len]``; defaults to its length) or ``None`` (the engine's seeded random frames;
-    defaults to ``env.num_envs``).  The episodes of several rounds equal those of one large batch bit for bit only if ``act_fn``
+    defaults to ``env.num_envs``).  ``normalizer``: a ``HipVecNormalize`` whose frozen statistics transform the observations the
+    policy sees (``env`` itself stays unwrapped, so the episode returns are raw).  The episodes of several rounds equal those of one large batch bit for bit only if ``act_fn``
     computes a row's action independently of the number of rows; a library GEMM does not promise that."""
     n_eval_episodes, frames = resolve_frames(env, n_eval_episodes, start_frames)
     ev = BatchEvaluator(env, compact=compact, sync_every=sync_every)
-    act_fn = policy_act_fn(model, env, deterministic=deterministic)
+    act_fn = normalized_act_fn(policy_act_fn(model, env, deterministic=deterministic), normalizer)
     results = []
     for first, cnt in plan_rounds(n_eval_episodes, env.num_envs):
         if frames is None:
@@ -338,24 +347,24 @@ def run_episodes(model, env, n_eval_episodes=None, start_frames="all", determini
 
 
 def evaluate_policy(model, env, n_eval_episodes=None, start_frames="all", deterministic=True, max_steps=None,
-                    return_episode_rewards=False, compact=True):
+                    return_episode_rewards=False, compact=True, normalizer=None):
     """``stable_baselines3.common.evaluation.evaluate_policy`` [EXT] on a batch env: ``(mean_reward, std_reward)``, or with
     ``return_episode_rewards`` the lists ``(episode_rewards, episode_lengths)`` in episode order.  When there are more episodes than
     envs the evaluator runs ceil(episodes / num_envs) rounds.  See ``run_episodes`` for ``start_frames``, ``BatchEvaluator``
-    for ``compact`` (``"all"`` also leaves finished Unitree G1 envs out of the launches; same numbers)."""
-    results = run_episodes(model, env, n_eval_episodes, start_frames, deterministic, max_steps, compact)
+    for ``compact`` (``"all"`` also leaves finished Unitree G1 envs out of the launches; same numbers) and for ``normalizer``."""
+    results = run_episodes(model, env, n_eval_episodes, start_frames, deterministic, max_steps, compact, normalizer=normalizer)
     if return_episode_rewards:
         return ([float(x) for r in results for x in _np(r.ep_ret)], [int(x) for r in results for x in _np(r.ep_len)])
     s = episode_statistics(results, max_ep_length(env))
     return s["ep_rew_mean"], s["ep_rew_std"]
 
 
-def evaluation_record(model, env, global_step, start_frames="all", n_eval_episodes=None, max_steps=None, compact="all"):
+def evaluation_record(model, env, global_step, start_frames="all", n_eval_episodes=None, max_steps=None, compact="all", normalizer=None):
     """The six fields of one evaluation point (``eval_batch.csv`` of ``EvalDashboardCallback``, ``"eval"`` of ``train.py --json``).
     ``compact="all"``: finished envs leave the launches on either robot (DESIGN §16 has the measurement behind the default)."""
     if is_combined(env) or (isinstance(start_frames, str) and is_multi_clip(env)):
         start_frames = None                                    # the combined task and a multi-clip env start from seeded random states
-    results = run_episodes(model, env, n_eval_episodes, start_frames, True, max_steps, compact)
+    results = run_episodes(model, env, n_eval_episodes, start_frames, True, max_steps, compact, normalizer=normalizer)
     return dict({"global_step": int(global_step)}, **episode_statistics(results, max_ep_length(env)))
 
 

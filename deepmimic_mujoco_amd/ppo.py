@@ -675,6 +675,7 @@ class PPO:
         self._last_obs = None
         self.stats = {}
         self._finish = None      # RolloutFinish (GAE + episode monitor + rollout statistics), made with the first rollout
+        self._finish_raw = None  # env wrapped in HipVecNormalize: the monitor over the raw rewards (``_finish`` sees the normalised ones)
         self._collector = None   # rollout.Collector: every piece of rollout state, made with the first rollout
 
     # ------------------------------------------------------------------ rollout
@@ -688,7 +689,7 @@ class PPO:
         """(returns, lengths) of the last <= 100 finished episodes, oldest first (SB3's ``ep_info_buffer``)."""
         if self._finish is None:
             return np.zeros(0, np.float32), np.zeros(0, np.float32)
-        r = self._finish.read()
+        r = (self._finish_raw or self._finish).read()
         return r["ep_returns"], r["ep_lengths"]
 
     def _fused_rollout_ok(self):
@@ -1060,4 +1061,6 @@ class PPO:
         self.num_timesteps = ck["num_timesteps"]
         if self._finish is not None:
             self._finish.reset()        # monitor state is not part of a checkpoint (nor is it in SB3): start it empty
+        if self._finish_raw is not None:
+            self._finish_raw.reset()
         return self

@@ -206,6 +206,9 @@ class Collector:
         self.chain_major = self.driver == "captured" and self.step_kind != "policy_forward"
         self.persistent = self.driver != "serial" or self.step_kind == "policy_forward"
         self.rb = self.last = self.graph = self.fwd = None
+        # a vec_normalize.HipVecNormalize around the env: the buffers gain a ``rew_raw`` row per step, which feeds the episode monitor
+        from .vec_normalize import HipVecNormalize
+        self.vn = env if isinstance(env, HipVecNormalize) else None
         self._scratch = {}
         if self.step_kind != "plain":
             # draw counters, advanced on the device: ONE PER SUB-BATCH — sub-batch chains run on their own streams (or as
@@ -225,6 +228,8 @@ class Collector:
                   logp=z(T, N), adv=z(T, N), ret=z(T, N))
         if self.step_kind == "policy_forward":
             rb["done_u8"] = z(T, N, dt=torch.uint8)         # dm_step writes its flags in place; the fp32 copy follows the finish
+        if self.vn is not None:
+            rb["rew_raw"] = z(T, N)                         # ``rew`` holds the normalised rewards (GAE), this the env's own (monitor)
         return rb
 
     # ---- the step of sub-batch k at time t, three kinds
@@ -235,7 +240,12 @@ class Collector:
         p, rb, sl, last = self.ppo, self.rb, self.slices[k], self.last
         self.fwd(last[sl], p._rollout_seed + 7919 * k, self.ctrs[0:1], t, p.act_lo, p.act_hi, rb["act"][t, sl], self.act_env[sl],
                  rb["logp"][t, sl], rb["val"][t, sl], obs_copy=rb["obs"][t, sl])
-        self.engines[k].step(self.act_env[sl], dict(obs=last[sl], rew=rb["rew"][t, sl], done=rb["done_u8"][t, sl]))
+        if self.vn is None:
+            self.engines[k].step(self.act_env[sl], dict(obs=last[sl], rew=rb["rew"][t, sl], done=rb["done_u8"][t, sl]))
+            return
+        # wrapped env (one engine): the raw reward goes to its own row, the normaliser then runs in place on what the engine wrote
+        self.engines[k].step(self.act_env[sl], dict(obs=last[sl], rew=rb["rew_raw"][t, sl], done=rb["done_u8"][t, sl]))
+        self.vn.step_inplace(last[sl], rb["rew_raw"][t, sl], rb["done_u8"][t, sl], rb["rew"][t, sl])
 
     def sample(self, obs, k=0):
         """mean / value by the MLP (library GEMMs), then one launch for sample + logp + clamp, keyed on sub-batch k's counter."""
@@ -263,6 +273,8 @@ class Collector:
         _lib.call("dm_rollout_store_bf16" if rb["obs"].dtype == torch.bfloat16 else "dm_rollout_store", val.shape[0], p.obs_dim, p.act_dim,
                   last[sl], sc["act"], val, sc["logp"], out["rew"], out["done"], out["obs"], rb["obs"][t, sl], rb["act"][t, sl],
                   rb["val"][t, sl], rb["logp"][t, sl], rb["rew"][t, sl], rb["done"][t, sl], last[sl], self.ctrs[k:k + 1], device=self.device)
+        if self.vn is not None:
+            rb["rew_raw"][t, sl].copy_(out["rew_raw"])
 
     def _step_plain(self, k, t):
         p, rb, sl, last = self.ppo, self.rb, self.slices[k], self.last
@@ -274,6 +286,8 @@ class Collector:
         rb["logp"][t, sl] = logp
         out = self._env_step(k, torch.clamp(act, p.act_lo, p.act_hi))
         rb["rew"][t, sl] = out["rew"]
+        if self.vn is not None:
+            rb["rew_raw"][t, sl] = out["rew_raw"]
         rb["done"][t, sl] = out["done"].float()
         last[sl].copy_(out["obs"])
 
@@ -313,6 +327,11 @@ class Collector:
         last_val = p.policy.predict_values(self.last)
         # GPU: dm_rollout_finish (bit for bit compute_gae), once over [T, N] after the streams joined; CPU: compute_gae itself
         p._finish(rb["rew"], rb.get("done_u8", rb["done"]), rb["val"], last_val, rb["adv"], rb["ret"])
+        if self.vn is not None:
+            # a Monitor inside VecNormalize sees the env's own rewards: a second finish fed rew_raw keeps the episode history and the
+            # reward mean; its advantages land in scratch rows and are not used
+            sc = self._scratch.setdefault("finish_raw", (torch.empty_like(rb["adv"]), torch.empty_like(rb["ret"])))
+            p._finish_raw(rb["rew_raw"], rb.get("done_u8", rb["done"]), rb["val"], last_val, *sc)
         if "done_u8" in rb:
             rb["done"].copy_(rb["done_u8"])     # the returned buffer's flags are fp32 on every route; nothing here waits for it
 
@@ -322,10 +341,11 @@ class Collector:
         p._last_obs = self.last
         p.num_timesteps += p.n_steps * p.n_envs
         r = p._finish.read()
-        p.stats.update(mean_reward=r["mean_reward"], done_rate=r["done_rate"], ep_rew_mean=r["ep_rew_mean"], ep_len_mean=r["ep_len_mean"],
-                       episodes=r["episodes"], explained_variance=r["explained_variance"])
+        m = r if self.vn is None else p._finish_raw.read()      # wrapped env: episodes and reward mean from the raw rewards
+        p.stats.update(mean_reward=m["mean_reward"], done_rate=r["done_rate"], ep_rew_mean=m["ep_rew_mean"], ep_len_mean=m["ep_len_mean"],
+                       episodes=m["episodes"], explained_variance=r["explained_variance"])
         if self.device.type != "cuda":                           # the torch path keeps its fp32 means
-            p.stats["mean_reward"] = float(rb["rew"].mean())
+            p.stats["mean_reward"] = float(rb["rew" if self.vn is None else "rew_raw"].mean())
             p.stats["done_rate"] = float(rb["done"].mean())
         return {k: v for k, v in rb.items() if k != "done_u8"}
 
@@ -339,6 +359,8 @@ class Collector:
             self.rb = self._alloc()
         if p._finish is None:
             p._finish = RolloutFinish(p.n_steps, p.n_envs, self.device, p.gamma, p.gae_lambda)
+        if self.vn is not None and p._finish_raw is None:
+            p._finish_raw = RolloutFinish(p.n_steps, p.n_envs, self.device, p.gamma, p.gae_lambda)
         with torch.no_grad():
             if self.driver == "captured":
                 if self.graph is None:

@@ -121,6 +121,10 @@ class SAC:
     def __init__(self, env, net_arch=(1024, 512), buffer_size=1_000_000, learning_starts=100, batch_size=256, tau=0.005, gamma=0.99,
                  train_freq=1, gradient_steps=1, ent_coef="auto", target_entropy="auto", learning_rate=3e-4, seed=0, device=None,
                  fused=True, use_hip_graph=True):
+        from .vec_normalize import HipVecNormalize
+        if isinstance(env, HipVecNormalize):
+            raise ValueError("SAC does not take a HipVecNormalize env: SB3 normalises at replay-sample time there, which this wrapper "
+                             "does not do; pass the inner env")
         self.env = env
         self.device = torch.device(device) if device is not None else getattr(env, "device", torch.device("cpu"))
         if isinstance(self.device, int):

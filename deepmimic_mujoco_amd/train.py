@@ -63,6 +63,12 @@ def build_parser():
                          "after each rollout the rings of envs whose step ended with a sim error or an out-of-bounds observation are "
                          "written to DIR as deepmimic_episode_<time>_env<i>.json")
     ap.add_argument("--debug-log-steps", type=int, default=64, help="--debug-log: steps kept per env")
+    ap.add_argument("--normalize", action="store_true",
+                    help="wrap the training env in HipVecNormalize (SB3's VecNormalize with the running statistics on the device, "
+                         "vec_normalize.py); --save P also writes P.vecnormalize, evaluations go through the frozen statistics; one rank only")
+    ap.add_argument("--norm-clip-obs", type=float, default=10.0, help="--normalize: clip_obs")
+    ap.add_argument("--norm-clip-reward", type=float, default=10.0, help="--normalize: clip_reward")
+    ap.add_argument("--no-norm-reward", action="store_true", help="--normalize: observations only (norm_reward=False)")
     ap.add_argument("--run-name", default="run")
     ap.add_argument("--eval-dir", default="~/deep_mimic")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
@@ -94,6 +100,10 @@ def main(argv=None):
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if args.algo == "sac" and world > 1:
         ap.error("--algo sac runs one learner on one GPU (SB3's SAC has no data-parallel mode): launch it without torch.distributed")
+    if args.normalize and world > 1:
+        ap.error("--normalize keeps one set of running statistics: with several ranks they would diverge per rank (SB3 has no counterpart)")
+    if args.normalize and args.algo == "sac":
+        ap.error("--normalize is PPO's: SB3's SAC normalises at replay-sample time, which is not implemented")
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     if world > 1:
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
@@ -125,6 +135,10 @@ def main(argv=None):
     dlog_dir = os.path.expanduser(args.debug_log) if world == 1 else os.path.join(os.path.expanduser(args.debug_log), "rank%d" % rank)
     if args.algo == "sac":
         return _train_sac(args, env, motions, local_rank)
+    vn = None
+    if args.normalize:
+        from .vec_normalize import HipVecNormalize
+        env = vn = HipVecNormalize(env, norm_reward=not args.no_norm_reward, clip_obs=args.norm_clip_obs, clip_reward=args.norm_clip_reward)
     ppo = PPO(env, net_arch=tuple(int(x) for x in args.arch.split(",")), n_steps=args.horizon,
               batch_size=args.minibatch, n_epochs=args.epochs, learning_rate=args.lr, seed=args.seed,
               buffer_dtype=torch.bfloat16 if args.bf16_buffer else torch.float32, rollout_graph=args.rollout_graph,
@@ -157,10 +171,12 @@ def main(argv=None):
     if rank == 0:
         if args.save:
             ppo.save(os.path.expanduser(args.save))
+            if vn is not None:
+                vn.save(os.path.expanduser(args.save) + ".vecnormalize")
         final_eval = None
         if batch_env is not None:                                       # the final policy, one deterministic episode per start frame
             from .evaluation import evaluation_record
-            final_eval = evaluation_record(ppo, batch_env, ppo.num_timesteps * world)
+            final_eval = evaluation_record(ppo, batch_env, ppo.num_timesteps * world, normalizer=vn)
             if not args.json:
                 print("final evaluation: %(episodes)d episodes  ep_rew_mean %(ep_rew_mean).3f +- %(ep_rew_std).3f  ep_len_mean %(ep_len_mean).1f  "
                       "reached the cap %(frac_reached_cap).2f" % final_eval, flush=True)
@@ -172,6 +188,7 @@ def main(argv=None):
             print(json.dumps({"workload": "ppo", "integrator": args.integrator, "n_gpus": world, "envs_per_gpu": args.envs, "horizon": args.horizon,
                               "arch": args.arch, "epochs": args.epochs, "minibatch": args.minibatch,
                               "buffer_dtype": str(ppo.buffer_dtype).replace("torch.", ""), "rollout_path": ppo.rollout_path(),
+                              "normalize": vn is not None,
                               "learner": ppo.learner_path(),
                               "iterations": len(hist), "rollout_env_steps_per_s": per_it / roll,
                               "train_s_per_iter": trn, "overall_env_steps_per_s": per_it / (roll + trn),
