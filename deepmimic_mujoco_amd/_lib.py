@@ -41,6 +41,8 @@ RENDER_EXPORTS = ["dm_render_create", "dm_render_destroy", "dm_render_last_error
 TRACE_EXPORTS = ["dm_trace_record", "dm_trace_mark", "dm_trace_last_error"]
 # include/deepmimic_vecnorm.h (csrc/dm_vecnorm.hip): SB3's VecNormalize, vec_normalize.HipVecNormalize
 VECNORM_EXPORTS = ["dm_vecnorm_scratch_bytes", "dm_vecnorm_step", "dm_vecnorm_reset", "dm_vecnorm_apply", "dm_vecnorm_last_error"]
+# include/deepmimic_sac_norm.h (csrc/dm_sac.hip): SAC's minibatch gather with VecNormalize applied at sample time, SAC(normalizer=)
+SAC_NORM_EXPORTS = ["dm_sac_gather_norm"]
 
 
 class DmConfig(C.Structure):
@@ -224,6 +226,8 @@ def load_library():
     L.dm_vecnorm_apply.argtypes = [C.POINTER(DmVecNorm), i32] + [vp] * 5
     L.dm_vecnorm_last_error.argtypes = []
     L.dm_vecnorm_last_error.restype = C.c_char_p
+    L.dm_sac_gather_norm.argtypes = L.dm_sac_gather.argtypes[:-1] + [C.POINTER(DmVecNorm), vp]
+    L.dm_sac_gather_norm.restype = C.c_int
     for name in EXPORTS:
         if name not in ("dm_default_config", "dm_last_error"):
             getattr(L, name).restype = C.c_longlong if name in ("dm_policy_packed_floats", "dm_ppo_mlp_workspace_floats", "dm_ppo_wide_packed_elems", "dm_ppo_wide3_packed_elems", "dm_rollout_finish_workspace_bytes") else C.c_int

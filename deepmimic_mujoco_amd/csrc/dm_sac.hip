@@ -20,6 +20,7 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "../../include/deepmimic_sac_norm.h"
 #include "dm_launch.h"
 #include "dm_rng.h"
 
@@ -158,6 +159,49 @@ __global__ void sac_gather_kernel(int B, int N, int D, int A, unsigned long long
   for (int c = threadIdx.x; c < A; c += blockDim.x) xq[(size_t)r * K + D + c] = r_act[i * A + c];
   if (threadIdx.x == 0) {
     rew[r] = r_rew[i];
+    done[r] = r_done[i];
+    if (idx_out) idx_out[r] = (int)i;
+  }
+}
+
+// ---- the same minibatch with SB3's VecNormalize applied at sample time (include/deepmimic_sac_norm.h): sac_gather_kernel's draw and
+// layouts, observations and next observations through normalize_obs, the reward through normalize_reward.  The statistics are read
+// here, through the pointers, so a replayed graph sees those of its moment; flags, epsilon and clips are launch arguments.  A thread
+// forms the mean and the scale of its column once (fp64 sqrt, fp64 division in dm_vn_norm_one: the expression of dm_vecnorm.hip's
+// normalise kernel, hence its bits) and uses them for both rows and all five destinations.  No barrier.
+struct SacNormArgs {
+  const double *obs_mean, *obs_var, *ret_stats;
+  double epsilon, clip_obs, clip_reward;
+  int norm_obs, norm_reward;
+};
+
+__global__ void sac_gather_norm_kernel(int B, int N, int D, int A, unsigned long long seed, const unsigned *counter, const unsigned *ring,
+                                       const float *r_obs, const float *r_act, const float *r_rew, const float *r_done,
+                                       const float *r_next, float *obs2, float *xq, float *xpi, float *xt, float *rew, float *done,
+                                       int *idx_out, SacNormArgs v) {
+  const int r = blockIdx.x;
+  if (r >= B) return;
+  const unsigned long long total = (unsigned long long)ring[1] * (unsigned long long)N;
+  const unsigned h = dm_hash32(seed, (unsigned)r, counter[0], SAC_GATHER_TAG);
+  const size_t i = (size_t)(((unsigned long long)h * total) >> 32);        // < total, as in sac_gather_kernel
+  const int K = D + A;
+  for (int c = threadIdx.x; c < D; c += blockDim.x) {
+    float o = r_obs[i * D + c], n = r_next[i * D + c];
+    if (v.norm_obs) {
+      const double mean = v.obs_mean[c], scale = sqrt(v.obs_var[c] + v.epsilon);
+      o = dm_vn_norm_one((double)o, mean, scale, v.clip_obs);
+      n = dm_vn_norm_one((double)n, mean, scale, v.clip_obs);
+    }
+    obs2[(size_t)r * D + c] = o;
+    obs2[(size_t)(B + r) * D + c] = n;
+    xq[(size_t)r * K + c] = o;
+    xpi[(size_t)r * K + c] = o;
+    xt[(size_t)r * K + c] = n;
+  }
+  for (int c = threadIdx.x; c < A; c += blockDim.x) xq[(size_t)r * K + D + c] = r_act[i * A + c];
+  if (threadIdx.x == 0) {
+    const float x = r_rew[i];
+    rew[r] = v.norm_reward ? dm_vn_norm_one((double)x, 0.0, sqrt(v.ret_stats[1] + v.epsilon), v.clip_reward) : x;
     done[r] = r_done[i];
     if (idx_out) idx_out[r] = (int)i;
   }
@@ -401,6 +445,22 @@ extern "C" int dm_sac_gather(int B, int N, int D, int A, unsigned long long seed
     return DM_EINVAL;
   hipLaunchKernelGGL(sac_gather_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, B, N, D, A, seed, counter, ring, r_obs, r_act, r_rew,
                      r_done, r_next, obs2, xq, xpi, xt, rew, done, idx_out);
+  return dm_launch_status();
+}
+
+extern "C" int dm_sac_gather_norm(int B, int N, int D, int A, unsigned long long seed, const unsigned *counter, const unsigned *ring,
+                                  const float *r_obs, const float *r_act, const float *r_rew, const float *r_done, const float *r_next,
+                                  float *obs2, float *xq, float *xpi, float *xt, float *rew, float *done, int *idx_out,
+                                  const DmVecNorm *vn, void *stream) {
+  if (B < 1 || N < 1 || D < 1 || A < 1 || !counter || !ring || !r_obs || !r_act || !r_rew || !r_done || !r_next || !obs2 || !xq ||
+      !xpi || !xt || !rew || !done)
+    return DM_EINVAL;
+  if (dm_vn_struct_error(vn) || vn->D != D) return DM_EINVAL;
+  // by value: the pointers (what they point at is read when the kernel runs) and the settings of this moment
+  const SacNormArgs v = {vn->obs_mean, vn->obs_var, vn->ret_stats, vn->epsilon, vn->clip_obs, vn->clip_reward,
+                         vn->norm_obs != 0, vn->norm_reward != 0};
+  hipLaunchKernelGGL(sac_gather_norm_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, B, N, D, A, seed, counter, ring, r_obs, r_act,
+                     r_rew, r_done, r_next, obs2, xq, xpi, xt, rew, done, idx_out, v);
   return dm_launch_status();
 }
 

@@ -198,12 +198,7 @@ struct NormArgs {
   int n, D, norm_obs, norm_reward, zero_returns;      // zero_returns: 1 = of done envs, 2 = of every env (reset)
 };
 
-__device__ __forceinline__ float norm_one(double x, double mean, double scale, double clip) {
-  double y = (x - mean) / scale;          // fp64 to the end: one rounding, at the cast
-  y = y < -clip ? -clip : (y > clip ? clip : y);
-  return (float)y;
-}
-
+// The transform itself is dm_vn_norm_one of the header (shared with dm_sac_gather_norm).
 // grid (row blocks of NORM_ROWS, column tiles); no barrier.  Thread (wave, lane) owns column tile * 64 + lane of rows wave, wave + 4,
 // ... of its block: it reads an element, then writes it, so in-place pointers are safe.  The first NORM_ROWS threads of the blocks
 // of column tile 0 handle the reward and the return of one row each.
@@ -220,11 +215,11 @@ __global__ void __launch_bounds__(BLOCK) vecnorm_normalize_kernel(NormArgs a) {
       const size_t at = (size_t)r * a.D + col;
       if (a.obs) {
         const float x = a.obs[at];
-        a.obs_out[at] = a.norm_obs ? norm_one((double)x, mean, scale, a.clip_obs) : x;
+        a.obs_out[at] = a.norm_obs ? dm_vn_norm_one((double)x, mean, scale, a.clip_obs) : x;
       }
       if (a.tobs) {
         const float x = a.tobs[at];
-        a.tobs_out[at] = (a.norm_obs && a.done[r] != 0) ? norm_one((double)x, mean, scale, a.clip_obs) : x;
+        a.tobs_out[at] = (a.norm_obs && a.done[r] != 0) ? dm_vn_norm_one((double)x, mean, scale, a.clip_obs) : x;
       }
     }
   }
@@ -233,7 +228,7 @@ __global__ void __launch_bounds__(BLOCK) vecnorm_normalize_kernel(NormArgs a) {
     if (r < a.n) {
       if (a.rew) {
         const float x = a.rew[r];
-        a.rew_out[r] = a.norm_reward ? norm_one((double)x, 0.0, sqrt(a.ret_stats[1] + a.epsilon), a.clip_reward) : x;
+        a.rew_out[r] = a.norm_reward ? dm_vn_norm_one((double)x, 0.0, sqrt(a.ret_stats[1] + a.epsilon), a.clip_reward) : x;
       }
       if (a.returns && (a.zero_returns == 2 || (a.zero_returns == 1 && a.done[r] != 0))) a.returns[r] = 0.0;
     }
@@ -242,13 +237,7 @@ __global__ void __launch_bounds__(BLOCK) vecnorm_normalize_kernel(NormArgs a) {
 
 int check(const DmVecNorm *v, bool stateful) {
   g_err[0] = 0;
-  if (!v) return refuse("null DmVecNorm");
-  if (v->N < 1 || v->D < 1) return refuse("N < 1 or D < 1");
-  if (v->device < 0) return refuse("device < 0");
-  if (!v->obs_mean || !v->obs_var || !v->obs_count || !v->ret_stats) return refuse("null statistics pointer in DmVecNorm");
-  if (!(v->gamma >= 0.0 && v->gamma <= 1.0)) return refuse("gamma outside [0, 1]");
-  if (!(v->epsilon >= 0.0)) return refuse("epsilon < 0");
-  if (!(v->clip_obs > 0.0) || !(v->clip_reward > 0.0)) return refuse("clip_obs or clip_reward <= 0");
+  if (const char *why = dm_vn_struct_error(v)) return refuse(why);
   if (stateful) {
     if (!v->returns || !v->scratch) return refuse("null returns or scratch in DmVecNorm");
     if (v->scratch_bytes < dm_vecnorm_scratch_bytes(v->N, v->D)) return refuse("scratch smaller than dm_vecnorm_scratch_bytes(N, D)");

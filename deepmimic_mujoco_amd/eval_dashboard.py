@@ -14,10 +14,11 @@ import numpy as np
 
 
 def training_normalizer(model):
-    """The ``HipVecNormalize`` the model trains through, or None: evaluation then goes through its frozen statistics."""
+    """The ``HipVecNormalize`` the model trains through, or None: evaluation then goes through its frozen statistics.  That is the
+    model's env when it is the wrapper (PPO), or ``model.normalizer`` (SAC, which normalises at replay-sample time)."""
     from .vec_normalize import HipVecNormalize
     env = getattr(model, "env", None)
-    return env if isinstance(env, HipVecNormalize) else None
+    return env if isinstance(env, HipVecNormalize) else getattr(model, "normalizer", None)
 
 
 def eval_dashboard_rollout(model, eval_env, n, run_name, log_wandb=False, out_root=None, max_steps=None, figures=True, normalizer=None):

@@ -13,10 +13,18 @@ Two learners compute the same update, SB3's SAC.train in its order (alpha step, 
     csrc/dm_sac.hip, all state on the device; one gradient step is captured once as a hipGraph and replayed.
 Parameters live in three flat fp32 arenas (actor, critic, critic target) shared by both learners; an env step is
 act + ``env.step_tensor`` + store, the replay ring never leaves HBM.
+
+``SAC(env, normalizer=HipVecNormalize(env))`` is SB3's SAC on a ``VecNormalize`` env [EXT: OffPolicyAlgorithm._store_transition,
+ReplayBuffer._get_samples]: the actor reads normalised observations, every env step feeds the running statistics, the ring stores RAW
+transitions (the raw terminal observation for a finished env) and each sampled minibatch is normalised with the statistics of that
+gradient step: ``dm_sac_gather_norm`` in the place of ``dm_sac_gather`` in the captured launch sequence, ``_norm_obs_t`` /
+``_norm_rew_t`` in ``sample_torch``.  The learner steps the inner env itself; ``normalizer.training = False`` freezes the statistics
+and keeps both transforms.  DESIGN §25.
 """
 from __future__ import annotations
 
 import collections
+import ctypes
 import math
 import time
 
@@ -120,12 +128,15 @@ class SacPolicy:
 class SAC:
     def __init__(self, env, net_arch=(1024, 512), buffer_size=1_000_000, learning_starts=100, batch_size=256, tau=0.005, gamma=0.99,
                  train_freq=1, gradient_steps=1, ent_coef="auto", target_entropy="auto", learning_rate=3e-4, seed=0, device=None,
-                 fused=True, use_hip_graph=True):
+                 fused=True, use_hip_graph=True, normalizer=None):
         from .vec_normalize import HipVecNormalize
         if isinstance(env, HipVecNormalize):
             raise ValueError("SAC does not take a HipVecNormalize env: SB3 normalises at replay-sample time there, which this wrapper "
                              "does not do; pass the inner env")
+        if normalizer is not None and not (isinstance(normalizer, HipVecNormalize) and normalizer.venv is env):
+            raise ValueError("SAC(env, normalizer=...) takes a HipVecNormalize built on that same env (normalizer.venv is env)")
         self.env = env
+        self.normalizer = normalizer
         self.device = torch.device(device) if device is not None else getattr(env, "device", torch.device("cpu"))
         if isinstance(self.device, int):
             self.device = torch.device("cuda", self.device)
@@ -181,7 +192,12 @@ class SAC:
         self._learn_seed = (0x5AC1EA12 + 104729 * seed) & 0x7FFFFFFFFFFFFFFF
         self._gen = torch.Generator(device=dev)
         self._gen.manual_seed(seed)
-        self._last_obs = None
+        self._last_obs = None                                              # raw: what the ring stores
+        # with a normaliser: what the actor reads (normalize_obs of _last_obs as of the step that produced it), and where the
+        # normalised reward of normalize_step_ goes (SAC uses the raw reward: the ring and the episode monitor)
+        self._obs_norm = torch.zeros(N, D, device=dev) if normalizer is not None else None
+        self._rew_scratch = z(N) if normalizer is not None else None
+        self._graph_norm_key = None
         self._pos = self._fill = 0                                         # torch path mirrors of ring_state[0:2]
         self.num_timesteps = 0
         self._n_updates = 0
@@ -261,29 +277,50 @@ class SAC:
                    out["obs"], out["terminal_obs"], R["obs"], R["act"], R["rew"], R["done"], R["next_obs"], self._last_obs,
                    self.ring_state, self._roll_ctr, self.ep_acc, self.ep_hist)
 
+    def _norm_after_step(self, out):
+        """SB3's VecNormalize.step_wait around the inner step SAC just made: statistics (when training, warm-up included) and the
+        next normalised observation.  The inner env's tensors stay raw."""
+        self.normalizer.normalize_step_(out["obs"], out["rew"], out["done"], None, self._obs_norm, self._rew_scratch, None)
+
     def env_step(self):
-        """One vec-env step: act (uniform before learning_starts) + env.step_tensor + store."""
+        """One vec-env step: act (uniform before learning_starts) + env.step_tensor + store.  With a normaliser the actor reads the
+        normalised last observation and the ring still gets the raw one."""
+        vn = self.normalizer
         if self._last_obs is None:
-            self._last_obs = self.env.reset_tensor().clone().contiguous()
+            if vn is None:
+                self._last_obs = self.env.reset_tensor().clone().contiguous()
+            else:
+                self._obs_norm.copy_(vn.reset_tensor())
+                self._last_obs = vn.out["obs_raw"].clone().contiguous()
+        seen = self._last_obs if vn is None else self._obs_norm
         warmup = self.num_timesteps < self.learning_starts
         if self.fused:
-            _, act_env = self._act_fused(self._last_obs, warmup)
+            _, act_env = self._act_fused(seen, warmup)
             out = self.env.step_tensor(act_env)
+            if vn is not None:
+                self._norm_after_step(out)
             self._store_fused(out)
         else:
             with torch.no_grad():
-                act, act_env = self._act_torch(self._last_obs, warmup)
+                act, act_env = self._act_torch(seen, warmup)
                 out = self.env.step_tensor(act_env)
+                if vn is not None:
+                    self._norm_after_step(out)
                 self.store_torch(self._last_obs, act, out)
                 self._last_obs = out["obs"].clone()
         self.num_timesteps += self.n_envs
 
     # ------------------------------------------------------------------ torch learner (SB3 SAC.train, one gradient step)
-    def sample_torch(self):
-        total = self._fill * self.n_envs
-        idx = torch.randint(0, total, (self.batch_size,), device=self.device, generator=self._gen)
-        R = self.ring
-        return dict(obs=R["obs"][idx], act=R["act"][idx], rew=R["rew"][idx], next_obs=R["next_obs"][idx], done=R["done"][idx])
+    def sample_torch(self, idx=None):
+        """A minibatch of ring rows ``idx`` (drawn uniformly when None); with a normaliser, SB3's ReplayBuffer._get_samples:
+        observations and rewards through the statistics of this moment, actions and done flags as stored."""
+        if idx is None:
+            idx = torch.randint(0, self._fill * self.n_envs, (self.batch_size,), device=self.device, generator=self._gen)
+        R, vn = self.ring, self.normalizer
+        b = dict(obs=R["obs"][idx], act=R["act"][idx], rew=R["rew"][idx], next_obs=R["next_obs"][idx], done=R["done"][idx])
+        if vn is not None:
+            b.update(obs=vn._norm_obs_t(b["obs"]), next_obs=vn._norm_obs_t(b["next_obs"]), rew=vn._norm_rew_t(b["rew"]))
+        return b
 
     def gradient_step_torch(self, batch=None, eps_pi=None, eps_next=None):
         """SB3's order: alpha (before its step), alpha step, target, critic step, actor loss on the stepped critics, actor step,
@@ -359,9 +396,13 @@ class SAC:
         Pa, Pc, Pt = self.policy.actor, self.policy.critic, self.policy.critic_target
         Ga, Gc = arena_views(fb["g_actor"], self._alay), arena_views(fb["g_critic"], self._clay)
         R = self.ring
-        # 1. minibatch
-        call("dm_sac_gather", B, self.n_envs, D, A, seed, ctr, self.ring_state, R["obs"], R["act"], R["rew"], R["done"], R["next_obs"],
-             fb["obs2"], fb["xq"], fb["xpi"], fb["xt"], fb["rew"], fb["done"], fb["idx"])
+        # 1. minibatch; with a normaliser the same rows, normalised inside the launch with the statistics it finds when it runs
+        gather = (B, self.n_envs, D, A, seed, ctr, self.ring_state, R["obs"], R["act"], R["rew"], R["done"], R["next_obs"],
+                  fb["obs2"], fb["xq"], fb["xpi"], fb["xt"], fb["rew"], fb["done"], fb["idx"])
+        if self.normalizer is None:
+            call("dm_sac_gather", *gather)
+        else:
+            call("dm_sac_gather_norm", *gather, ctypes.byref(self.normalizer._desc))
         # 2-4. one actor pass over (obs ; next_obs), squashed heads (a_pi, a'), alpha and its Adam step
         call("dm_sac_linear_relu", fb["obs2"], D, Pa["W1"], Pa["b1"], fb["h1a"], 2 * B, H1, D, 1)
         torch.addmm(Pa["b2"], fb["h1a"], Pa["W2"].t(), out=fb["h2a"]).relu_()
@@ -411,15 +452,23 @@ class SAC:
     def _capture(self):
         """Capture gradient_step_fused once.  The warm-up step (library handles, workspaces) runs on a side stream and is undone."""
         snap = [t.clone() for t in self.state_tensors()]
+        self._graph_norm_key = self._norm_key()
         self._graph, _ = capture_graph(self.device, self.gradient_step_fused, warm=self.gradient_step_fused)
         with torch.no_grad():
             for t, s in zip(self.state_tensors(), snap):
                 t.copy_(s)
 
+    def _norm_key(self):
+        """What dm_sac_gather_norm takes by value, so what a captured graph holds of the normaliser (its statistics it reads anew)."""
+        vn = self.normalizer
+        return None if vn is None else (vn.norm_obs, vn.norm_reward, vn.clip_obs, vn.clip_reward, vn.epsilon)
+
     def train(self, gradient_steps):
         for _ in range(gradient_steps):
             if self.fused:
                 if self.use_hip_graph:
+                    if self._graph is not None and self._graph_norm_key != self._norm_key():
+                        self._graph = None                     # a flag, a clip or epsilon changed since the capture
                     if self._graph is None:
                         self._capture()
                     self._graph.replay()

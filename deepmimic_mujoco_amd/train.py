@@ -64,8 +64,10 @@ def build_parser():
                          "written to DIR as deepmimic_episode_<time>_env<i>.json")
     ap.add_argument("--debug-log-steps", type=int, default=64, help="--debug-log: steps kept per env")
     ap.add_argument("--normalize", action="store_true",
-                    help="wrap the training env in HipVecNormalize (SB3's VecNormalize with the running statistics on the device, "
-                         "vec_normalize.py); --save P also writes P.vecnormalize, evaluations go through the frozen statistics; one rank only")
+                    help="train through HipVecNormalize (SB3's VecNormalize with the running statistics on the device, vec_normalize.py): "
+                         "PPO's env is wrapped; --algo sac keeps the raw env, stores raw transitions and normalises every sampled minibatch "
+                         "inside the gather launch (SAC(normalizer=)); --save P also writes P.vecnormalize, evaluations go through the "
+                         "frozen statistics; one rank only")
     ap.add_argument("--norm-clip-obs", type=float, default=10.0, help="--normalize: clip_obs")
     ap.add_argument("--norm-clip-reward", type=float, default=10.0, help="--normalize: clip_reward")
     ap.add_argument("--no-norm-reward", action="store_true", help="--normalize: observations only (norm_reward=False)")
@@ -102,8 +104,6 @@ def main(argv=None):
         ap.error("--algo sac runs one learner on one GPU (SB3's SAC has no data-parallel mode): launch it without torch.distributed")
     if args.normalize and world > 1:
         ap.error("--normalize keeps one set of running statistics: with several ranks they would diverge per rank (SB3 has no counterpart)")
-    if args.normalize and args.algo == "sac":
-        ap.error("--normalize is PPO's: SB3's SAC normalises at replay-sample time, which is not implemented")
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     if world > 1:
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
@@ -209,8 +209,12 @@ def main(argv=None):
 def _train_sac(args, env, motions, local_rank):
     """src/sac_sb3.py: SAC(MlpPolicy, net_arch=[1024, 512] by --arch, buffer_size) with SB3's other defaults; one learner."""
     from .sac import SAC
+    vn = None
+    if args.normalize:                              # on the inner env: SAC normalises at replay-sample time, not at store time
+        from .vec_normalize import HipVecNormalize
+        vn = HipVecNormalize(env, norm_reward=not args.no_norm_reward, clip_obs=args.norm_clip_obs, clip_reward=args.norm_clip_reward)
     sac = SAC(env, net_arch=tuple(int(x) for x in args.arch.split(",")), buffer_size=args.buffer_size,
-              learning_starts=args.learning_starts, gradient_steps=args.gradient_steps, seed=args.seed)
+              learning_starts=args.learning_starts, gradient_steps=args.gradient_steps, seed=args.seed, normalizer=vn)
     hist = []
     dash = None
     batch_env = _eval_batch_env(args, motions, local_rank) if args.eval_envs > 0 else None
@@ -244,15 +248,17 @@ def _train_sac(args, env, motions, local_rank):
     dt = time.perf_counter() - t0
     if args.save:
         sac.save(os.path.expanduser(args.save))
+        if vn is not None:
+            vn.save(os.path.expanduser(args.save) + ".vecnormalize")
     final_eval = None
     if batch_env is not None:
         from .evaluation import evaluation_record
-        final_eval = evaluation_record(sac, batch_env, sac.num_timesteps)
+        final_eval = evaluation_record(sac, batch_env, sac.num_timesteps, normalizer=vn)
         batch_env.close()
     if args.json:
         last = hist[-1] if hist else {}
         print(json.dumps({"workload": "sac", "integrator": args.integrator, "envs": env.num_envs, "arch": args.arch, "buffer_size": args.buffer_size,
-                          "gradient_steps": args.gradient_steps, "total_timesteps": sac.num_timesteps, "n_updates": sac._n_updates,
+                          "gradient_steps": args.gradient_steps, "normalize": vn is not None, "total_timesteps": sac.num_timesteps, "n_updates": sac._n_updates,
                           "env_steps_per_s": sac.num_timesteps / dt, "wall_s": dt,
                           "ep_rew_mean": last.get("ep_rew_mean"), "ep_len_mean": last.get("ep_len_mean"),
                           "critic_loss": last.get("critic_loss"), "actor_loss": last.get("actor_loss"), "ent_coef": last.get("ent_coef"),

@@ -9,8 +9,11 @@ no ``step_sub`` here, so ``rollout.route`` takes the serial driver and the stati
 
 On a CPU device the same arithmetic runs as torch fp64 ops (the wrapper's logic is testable without a GPU over any object that
 offers ``reset_tensor`` / ``step_tensor`` / ``num_envs`` / ``device`` / the two spaces).  The semantics are restated in numpy in
-tests/vecnorm_ref.py.  The flags ``training`` / ``norm_obs`` / ``norm_reward`` may be set between steps; a rollout graph captured
-earlier keeps the values it was captured with.
+tests/vecnorm_ref.py.  The flags ``training`` / ``norm_obs`` / ``norm_reward`` and the settings ``clip_obs`` / ``clip_reward`` /
+``gamma`` / ``epsilon`` may be set between steps; a rollout graph captured earlier keeps the values it was captured with.
+
+``SAC(env, normalizer=HipVecNormalize(env))`` is the off-policy use (sac.py): the learner steps the inner env itself, feeds
+``normalize_step_`` for the statistics and the actor's observation, stores raw transitions and normalises each sampled minibatch.
 """
 from __future__ import annotations
 
@@ -105,6 +108,20 @@ class HipVecNormalize:
 
     training, norm_obs, norm_reward = _flag("training"), _flag("norm_obs"), _flag("norm_reward")
     del _flag
+
+    # ---- so do the four settings: one changed between steps reaches the next launch (and SAC's sample-time transform)
+    def _setting(name):
+        def get(self):
+            return self.__dict__["_" + name]
+
+        def set_(self, v):
+            self.__dict__["_" + name] = float(v)
+            if self.__dict__.get("_desc") is not None:
+                setattr(self._desc, name, float(v))
+        return property(get, set_)
+
+    clip_obs, clip_reward, gamma, epsilon = _setting("clip_obs"), _setting("clip_reward"), _setting("gamma"), _setting("epsilon")
+    del _setting
 
     def __getattr__(self, name):
         """Everything else of the VecEnv surface (``seed``, ``get_attr``, ``render``, ``enable_debug_log``, ``sub_batches`` ...) is
@@ -337,9 +354,6 @@ class HipVecNormalize:
             self.returns.zero_()
         if settings:
             self.clip_obs, self.clip_reward, self.gamma, self.epsilon = (float(x) for x in np.asarray(sd["settings"]).reshape(-1))
-            if self._desc is not None:
-                self._desc.clip_obs, self._desc.clip_reward = self.clip_obs, self.clip_reward
-                self._desc.gamma, self._desc.epsilon = self.gamma, self.epsilon
             self.training, self.norm_obs, self.norm_reward = (bool(x) for x in np.asarray(sd["flags"]).reshape(-1))
 
     def save(self, path):

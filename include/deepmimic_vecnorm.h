@@ -62,4 +62,28 @@ const char* dm_vecnorm_last_error(void);
 #ifdef __cplusplus
 }
 #endif
+
+#ifdef __HIPCC__
+/* For the translation units of the library that apply the transform inside a kernel of their own (csrc/dm_vecnorm.hip, and
+ * dm_sac_gather_norm of csrc/dm_sac.hip: include/deepmimic_sac_norm.h): the ONE statement of it and of the struct checks, so that
+ * what a replay minibatch gets is bit for bit what dm_vecnorm_apply gives.  `scale` is sqrt(var + epsilon), formed once per column
+ * by the caller; the reward passes mean 0.  fp64 to the end: one rounding, at the cast. */
+__device__ __forceinline__ float dm_vn_norm_one(double x, double mean, double scale, double clip) {
+  double y = (x - mean) / scale;
+  y = y < -clip ? -clip : (y > clip ? clip : y);
+  return (float)y;
+}
+
+/* Why the fields every entry point reads are refused, or NULL when they are fine (`returns` and `scratch` are not looked at). */
+static inline const char* dm_vn_struct_error(const DmVecNorm* v) {
+  if (!v) return "null DmVecNorm";
+  if (v->N < 1 || v->D < 1) return "N < 1 or D < 1";
+  if (v->device < 0) return "device < 0";
+  if (!v->obs_mean || !v->obs_var || !v->obs_count || !v->ret_stats) return "null statistics pointer in DmVecNorm";
+  if (!(v->gamma >= 0.0 && v->gamma <= 1.0)) return "gamma outside [0, 1]";
+  if (!(v->epsilon >= 0.0)) return "epsilon < 0";
+  if (!(v->clip_obs > 0.0) || !(v->clip_reward > 0.0)) return "clip_obs or clip_reward <= 0";
+  return 0;
+}
+#endif
 #endif
