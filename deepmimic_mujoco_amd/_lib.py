@@ -40,9 +40,15 @@ RENDER_EXPORTS = ["dm_render_create", "dm_render_destroy", "dm_render_last_error
 # include/deepmimic_trace.h (csrc/dm_trace.hip): the episode debug log, debug_log.FlightRecorder
 TRACE_EXPORTS = ["dm_trace_record", "dm_trace_mark", "dm_trace_last_error"]
 # include/deepmimic_vecnorm.h (csrc/dm_vecnorm.hip): SB3's VecNormalize, vec_normalize.HipVecNormalize
-VECNORM_EXPORTS = ["dm_vecnorm_scratch_bytes", "dm_vecnorm_step", "dm_vecnorm_reset", "dm_vecnorm_apply", "dm_vecnorm_last_error"]
+VECNORM_EXPORTS = ["dm_vecnorm_scratch_bytes", "dm_vecnorm_step", "dm_vecnorm_reset", "dm_vecnorm_apply", "dm_vecnorm_last_error",
+                   "dm_vecnorm_step_sync", "dm_vecnorm_reset_sync", "dm_vecnorm_sync_pack", "dm_vecnorm_sync_merge"]
 # include/deepmimic_sac_norm.h (csrc/dm_sac.hip): SAC's minibatch gather with VecNormalize applied at sample time, SAC(normalizer=)
 SAC_NORM_EXPORTS = ["dm_sac_gather_norm"]
+
+
+class DmVecNormSync(C.Structure):
+    """include/deepmimic_vecnorm.h: DmVecNormSync"""
+    _fields_ = [("world", C.c_int32), ("rank", C.c_int32), ("base", C.c_void_p), ("acc", C.c_void_p), ("gather", C.c_void_p)]
 
 
 class DmConfig(C.Structure):
@@ -225,6 +231,10 @@ def load_library():
     L.dm_vecnorm_reset.argtypes = [C.POINTER(DmVecNorm)] + [vp] * 3
     L.dm_vecnorm_apply.argtypes = [C.POINTER(DmVecNorm), i32] + [vp] * 5
     L.dm_vecnorm_last_error.argtypes = []
+    L.dm_vecnorm_step_sync.argtypes = [C.POINTER(DmVecNorm)] + [vp] * 7 + [C.POINTER(DmVecNormSync), vp]
+    L.dm_vecnorm_reset_sync.argtypes = [C.POINTER(DmVecNorm)] + [vp] * 2 + [C.POINTER(DmVecNormSync), vp]
+    L.dm_vecnorm_sync_pack.argtypes = [C.POINTER(DmVecNorm), C.POINTER(DmVecNormSync), vp]
+    L.dm_vecnorm_sync_merge.argtypes = [C.POINTER(DmVecNorm), C.POINTER(DmVecNormSync), vp]
     L.dm_vecnorm_last_error.restype = C.c_char_p
     L.dm_sac_gather_norm.argtypes = L.dm_sac_gather.argtypes[:-1] + [C.POINTER(DmVecNorm), vp]
     L.dm_sac_gather_norm.restype = C.c_int

@@ -1,7 +1,9 @@
 // dm_vecnorm.hip — SB3's VecNormalize on the device (include/deepmimic_vecnorm.h): fp64 running mean / variance of the observation
 // columns and of the discounted returns, and the clipped transforms.  Shares nothing with the engines.  A training step is three
 // launches: moments of row chunks, their merge in ascending chunk order into the running statistics, the transform.
-// No atomics, no order that depends on timing: every sum is formed by one thread in index order.
+// No atomics, no order that depends on timing: every sum is formed by one thread in index order.  The _sync entry points keep the
+// statistics as base (agreed by all ranks) + acc (this rank's since then) and rebuild the running set from them; every
+// merge of theirs is dm_vn_merge of the header.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 
@@ -121,12 +123,16 @@ struct UpdateArgs {
   const double *part;
   double *obs_mean, *obs_var, *obs_count, *ret_stats;
   int N, D, col0, ncols, rows, chunks;
+  const double *base;       // SYNC only: [2 D + 4], read
+  double *acc;              // SYNC only: [2 D + 4]; the moments launch copied ITS observation count behind part
 };
 
 // grid: column tiles.  Wave w of sixteen merges its contiguous share of the chunks of column col0 + tile * 64 + lane in ascending
 // order, wave 0 then merges the sixteen partial results in ascending order and folds the batch (mean, population variance, N) into the
 // running statistics as RunningMeanStd.update_from_moments does.  One barrier, at the top level.  The observation count is read from
 // the copy the moments launch left behind part, so the one thread that rewrites it races with no reader.
+// SYNC: the batch is folded into acc instead, and the running statistics are rewritten as merge(base, acc); base is only read.
+template <bool SYNC>
 __global__ void __launch_bounds__(UPD_BLOCK) vecnorm_update_kernel(UpdateArgs a) {
   __shared__ double s_mean[UPD_WAVES][TILE], s_m2[UPD_WAVES][TILE];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -171,6 +177,29 @@ __global__ void __launch_bounds__(UPD_BLOCK) vecnorm_update_kernel(UpdateArgs a)
     const double nb = (double)a.N;
     const double bv = q / nb;
     const bool is_ret = col == a.D;
+    if constexpr (SYNC) {
+      const int at_m = is_ret ? 2 * a.D + 1 : col, at_v = is_ret ? 2 * a.D + 2 : a.D + col, at_c = is_ret ? 2 * a.D + 3 : 2 * a.D;
+      double am = a.acc[at_m], av = a.acc[at_v], ac = is_ret ? a.acc[at_c] : obs_count;
+      dm_vn_merge(am, av, ac, m, bv, nb);
+      double rm = a.base[at_m], rv = a.base[at_v], rc = a.base[at_c];
+      dm_vn_merge(rm, rv, rc, am, av, ac);
+      a.acc[at_m] = am;
+      a.acc[at_v] = av;
+      if (is_ret) {
+        a.acc[at_c] = ac;
+        a.ret_stats[0] = rm;
+        a.ret_stats[1] = rv;
+        a.ret_stats[2] = rc;
+      } else {
+        a.obs_mean[col] = rm;
+        a.obs_var[col] = rv;
+        if (col == 0) {                                  // the one writer of both observation counts; every reader took the copy
+          a.acc[at_c] = ac;
+          a.obs_count[0] = rc;
+        }
+      }
+      return;                                            // past the only barrier
+    }
     const double mean = is_ret ? a.ret_stats[0] : a.obs_mean[col], var = is_ret ? a.ret_stats[1] : a.obs_var[col];
     const double count = is_ret ? a.ret_stats[2] : obs_count;
     const double d = m - mean, tot = count + nb;
@@ -185,7 +214,70 @@ __global__ void __launch_bounds__(UPD_BLOCK) vecnorm_update_kernel(UpdateArgs a)
       a.obs_var[col] = new_var;
     }
   }
-  if (blockIdx.x == 0 && threadIdx.x == 0 && a.col0 == 0) a.obs_count[0] = obs_count + (double)a.N;
+  if (!SYNC && blockIdx.x == 0 && threadIdx.x == 0 && a.col0 == 0) a.obs_count[0] = obs_count + (double)a.N;
+}
+
+// grid: blocks over the world * (2 D + 4) doubles of gather.  Row `rank` = acc, every other row = 0.
+__global__ void __launch_bounds__(BLOCK) vecnorm_sync_pack_kernel(const double *acc, double *gather, int S, int world, int rank) {
+  const long long i = (long long)blockIdx.x * BLOCK + threadIdx.x;
+  if (i >= (long long)world * S) return;
+  const int r = (int)(i / S), j = (int)(i - (long long)r * S);
+  gather[i] = r == rank ? acc[j] : 0.0;
+}
+
+struct SyncMergeArgs {
+  const double *gather;
+  double *base, *acc, *obs_mean, *obs_var, *obs_count, *ret_stats;
+  int D, world;
+};
+
+constexpr int MERGE_ROWS = 8;             // rows of gather in flight per column before their merges start
+
+// One block.  A thread owns column col of the virtual table (col = D: the returns), col + BLOCK, ...: it loads MERGE_ROWS rows of its
+// column at a time (independent loads, consecutive lanes on consecutive addresses, the counts one address per wave) and merges them
+// into base in ascending rank order; only that arithmetic is a chain.  Then running = base and acc = empty.  The old observation count
+// of base is read by every thread before the one barrier and written after it.
+__global__ void __launch_bounds__(BLOCK) vecnorm_sync_merge_kernel(SyncMergeArgs a) {
+  const int D = a.D, S = 2 * D + 4;
+  const double obs_count = a.base[2 * D];
+  __syncthreads();
+  for (int col = threadIdx.x; col <= D; col += BLOCK) {
+    const bool is_ret = col == D;
+    const int at_m = is_ret ? 2 * D + 1 : col, at_v = is_ret ? 2 * D + 2 : D + col, at_c = is_ret ? 2 * D + 3 : 2 * D;
+    double m = a.base[at_m], v = a.base[at_v], c = is_ret ? a.base[at_c] : obs_count;
+    for (int r0 = 0; r0 < a.world; r0 += MERGE_ROWS) {
+      double gm[MERGE_ROWS], gv[MERGE_ROWS], gc[MERGE_ROWS];
+#pragma unroll
+      for (int k = 0; k < MERGE_ROWS; k++) {
+        const bool in = r0 + k < a.world;
+        const double *row = a.gather + (size_t)(in ? r0 + k : 0) * S;
+        gm[k] = row[at_m];
+        gv[k] = row[at_v];
+        gc[k] = in ? row[at_c] : 0.0;                    // count 0: skipped
+      }
+#pragma unroll
+      for (int k = 0; k < MERGE_ROWS; k++) dm_vn_merge(m, v, c, gm[k], gv[k], gc[k]);
+    }
+    a.base[at_m] = m;
+    a.base[at_v] = v;
+    a.acc[at_m] = 0.0;
+    a.acc[at_v] = 0.0;
+    if (is_ret) {
+      a.base[at_c] = c;
+      a.acc[at_c] = 0.0;
+      a.ret_stats[0] = m;
+      a.ret_stats[1] = v;
+      a.ret_stats[2] = c;
+    } else {
+      a.obs_mean[col] = m;
+      a.obs_var[col] = v;
+      if (col == 0) {
+        a.base[at_c] = c;
+        a.acc[at_c] = 0.0;
+        a.obs_count[0] = c;
+      }
+    }
+  }
 }
 
 struct NormArgs {
@@ -245,6 +337,13 @@ int check(const DmVecNorm *v, bool stateful) {
   return DM_VECNORM_OK;
 }
 
+int check_sync(const DmVecNorm *v, const DmVecNormSync *y, bool stateful) {
+  const int rc = check(v, stateful);
+  if (rc != DM_VECNORM_OK) return rc;
+  if (const char *why = dm_vn_sync_error(y)) return refuse(why);
+  return DM_VECNORM_OK;
+}
+
 int launch_status() {
   if (hipGetLastError() == hipSuccess) return DM_VECNORM_OK;
   snprintf(g_err, sizeof g_err, "a launch was refused");
@@ -252,12 +351,17 @@ int launch_status() {
 }
 
 // the two statistics launches over columns [col0, col0 + ncols) of the virtual table
-void launch_update(const DmVecNorm *v, const float *obs, const float *rew, int col0, int ncols, hipStream_t s) {
+// `y`: the _sync entry points; the observation count the moments launch copies for the update launch is then acc's
+void launch_update(const DmVecNorm *v, const float *obs, const float *rew, int col0, int ncols, hipStream_t s, const DmVecNormSync *y = nullptr) {
   const int rows = chunk_rows(v->N), chunks = chunk_count(v->N);
-  const MomentsArgs m = {obs, rew, v->obs_count, v->returns, v->scratch, v->gamma, v->N, v->D, col0, ncols, rows, chunks};
+  const MomentsArgs m = {obs, rew, y ? y->acc + 2 * v->D : v->obs_count, v->returns, v->scratch, v->gamma, v->N, v->D, col0, ncols, rows, chunks};
   hipLaunchKernelGGL(vecnorm_moments_kernel, dim3(chunks, (ncols + TILE - 1) / TILE), dim3(BLOCK), 0, s, m);
-  const UpdateArgs u = {v->scratch, v->obs_mean, v->obs_var, v->obs_count, v->ret_stats, v->N, v->D, col0, ncols, rows, chunks};
-  hipLaunchKernelGGL(vecnorm_update_kernel, dim3((ncols + TILE - 1) / TILE), dim3(UPD_BLOCK), 0, s, u);
+  const UpdateArgs u = {v->scratch, v->obs_mean, v->obs_var, v->obs_count, v->ret_stats, v->N, v->D, col0, ncols, rows, chunks,
+                        y ? y->base : nullptr, y ? y->acc : nullptr};
+  if (y)
+    hipLaunchKernelGGL(vecnorm_update_kernel<true>, dim3((ncols + TILE - 1) / TILE), dim3(UPD_BLOCK), 0, s, u);
+  else
+    hipLaunchKernelGGL(vecnorm_update_kernel<false>, dim3((ncols + TILE - 1) / TILE), dim3(UPD_BLOCK), 0, s, u);
 }
 
 void launch_normalize(const NormArgs &a, hipStream_t s) {
@@ -272,16 +376,17 @@ extern "C" long long dm_vecnorm_scratch_bytes(int N, int D) {
   return ((long long)chunk_count(N) * 2 * ((long long)D + 1) + 1) * (long long)sizeof(double);
 }
 
-extern "C" int dm_vecnorm_step(const DmVecNorm *v, const float *obs, const float *rew, const uint8_t *done, const float *tobs,
-                               float *obs_out, float *rew_out, float *tobs_out, void *stream) {
-  const int rc = check(v, true);
-  if (rc != DM_VECNORM_OK) return rc;
+namespace {
+
+// dm_vecnorm_step (y = NULL) and dm_vecnorm_step_sync after their struct checks
+int step_checked(const DmVecNorm *v, const float *obs, const float *rew, const uint8_t *done, const float *tobs, float *obs_out,
+                 float *rew_out, float *tobs_out, const DmVecNormSync *y, void *stream) {
   if (!obs || !rew || !done || !obs_out || !rew_out) return refuse("null step input or output");
   if ((tobs == nullptr) != (tobs_out == nullptr)) return refuse("tobs and tobs_out are given together or not at all");
   if (hipSetDevice(v->device) != hipSuccess) return DM_VECNORM_EHIP;
   if (v->training) {
     const int col0 = v->norm_obs ? 0 : v->D;             // the return column is updated whenever training
-    launch_update(v, obs, rew, col0, v->D + 1 - col0, (hipStream_t)stream);
+    launch_update(v, obs, rew, col0, v->D + 1 - col0, (hipStream_t)stream, y);
   }
   // an identity that would copy a buffer onto itself is left out
   const bool obs_same = !v->norm_obs && obs == obs_out, tobs_same = !v->norm_obs && tobs == tobs_out;
@@ -293,17 +398,59 @@ extern "C" int dm_vecnorm_step(const DmVecNorm *v, const float *obs, const float
   return launch_status();
 }
 
-extern "C" int dm_vecnorm_reset(const DmVecNorm *v, const float *obs, float *obs_out, void *stream) {
-  const int rc = check(v, true);
-  if (rc != DM_VECNORM_OK) return rc;
+int reset_checked(const DmVecNorm *v, const float *obs, float *obs_out, const DmVecNormSync *y, void *stream) {
   if (!obs || !obs_out) return refuse("null reset input or output");
   if (hipSetDevice(v->device) != hipSuccess) return DM_VECNORM_EHIP;
-  if (v->training && v->norm_obs) launch_update(v, obs, nullptr, 0, v->D, (hipStream_t)stream);
+  if (v->training && v->norm_obs) launch_update(v, obs, nullptr, 0, v->D, (hipStream_t)stream, y);
   const bool obs_same = !v->norm_obs && obs == obs_out;
   const NormArgs a = {obs_same ? nullptr : obs, nullptr, nullptr, obs_out, nullptr, nullptr, nullptr,
                       v->obs_mean, v->obs_var, v->ret_stats, v->returns, v->epsilon, v->clip_obs, v->clip_reward,
                       v->N, v->D, v->norm_obs, v->norm_reward, 2};
   launch_normalize(a, (hipStream_t)stream);
+  return launch_status();
+}
+
+}  // namespace
+
+extern "C" int dm_vecnorm_step(const DmVecNorm *v, const float *obs, const float *rew, const uint8_t *done, const float *tobs,
+                               float *obs_out, float *rew_out, float *tobs_out, void *stream) {
+  const int rc = check(v, true);
+  return rc != DM_VECNORM_OK ? rc : step_checked(v, obs, rew, done, tobs, obs_out, rew_out, tobs_out, nullptr, stream);
+}
+
+extern "C" int dm_vecnorm_step_sync(const DmVecNorm *v, const float *obs, const float *rew, const uint8_t *done, const float *tobs,
+                                    float *obs_out, float *rew_out, float *tobs_out, const DmVecNormSync *y, void *stream) {
+  const int rc = check_sync(v, y, true);
+  return rc != DM_VECNORM_OK ? rc : step_checked(v, obs, rew, done, tobs, obs_out, rew_out, tobs_out, y, stream);
+}
+
+extern "C" int dm_vecnorm_reset(const DmVecNorm *v, const float *obs, float *obs_out, void *stream) {
+  const int rc = check(v, true);
+  return rc != DM_VECNORM_OK ? rc : reset_checked(v, obs, obs_out, nullptr, stream);
+}
+
+extern "C" int dm_vecnorm_reset_sync(const DmVecNorm *v, const float *obs, float *obs_out, const DmVecNormSync *y, void *stream) {
+  const int rc = check_sync(v, y, true);
+  return rc != DM_VECNORM_OK ? rc : reset_checked(v, obs, obs_out, y, stream);
+}
+
+extern "C" int dm_vecnorm_sync_pack(const DmVecNorm *v, const DmVecNormSync *y, void *stream) {
+  const int rc = check_sync(v, y, false);
+  if (rc != DM_VECNORM_OK) return rc;
+  if (hipSetDevice(v->device) != hipSuccess) return DM_VECNORM_EHIP;
+  const int S = 2 * v->D + 4;
+  const long long total = (long long)y->world * S;
+  hipLaunchKernelGGL(vecnorm_sync_pack_kernel, dim3((unsigned)((total + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, (hipStream_t)stream, y->acc,
+                     y->gather, S, y->world, y->rank);
+  return launch_status();
+}
+
+extern "C" int dm_vecnorm_sync_merge(const DmVecNorm *v, const DmVecNormSync *y, void *stream) {
+  const int rc = check_sync(v, y, false);
+  if (rc != DM_VECNORM_OK) return rc;
+  if (hipSetDevice(v->device) != hipSuccess) return DM_VECNORM_EHIP;
+  const SyncMergeArgs a = {y->gather, y->base, y->acc, v->obs_mean, v->obs_var, v->obs_count, v->ret_stats, v->D, y->world};
+  hipLaunchKernelGGL(vecnorm_sync_merge_kernel, dim3(1), dim3(BLOCK), 0, (hipStream_t)stream, a);
   return launch_status();
 }
 

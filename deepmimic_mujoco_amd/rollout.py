@@ -368,4 +368,9 @@ class Collector:
                 self.graph.replay()
             else:
                 self._whole()
+            if self.vn is not None and self.vn.synced:
+                # one set of running statistics over the ranks: once per rollout, after it and before train; eager and on the
+                # rollout stream like FlatAdam.all_reduce, outside the captured graph (two launches around one small all-reduce)
+                self.vn.sync()
+                p.stats["vecnorm_sync_calls"] = self.vn.sync_calls
         return self._tail()

@@ -67,7 +67,9 @@ def build_parser():
                     help="train through HipVecNormalize (SB3's VecNormalize with the running statistics on the device, vec_normalize.py): "
                          "PPO's env is wrapped; --algo sac keeps the raw env, stores raw transitions and normalises every sampled minibatch "
                          "inside the gather launch (SAC(normalizer=)); --save P also writes P.vecnormalize, evaluations go through the "
-                         "frozen statistics; one rank only")
+                         "frozen statistics; with several ranks (PPO) every rank folds its own rows into the agreed statistics and the "
+                         "ranks merge them once per rollout (HipVecNormalize(sync_group=\"world\"): two launches around one small "
+                         "all-reduce), P.vecnormalize is rank 0's after a final merge")
     ap.add_argument("--norm-clip-obs", type=float, default=10.0, help="--normalize: clip_obs")
     ap.add_argument("--norm-clip-reward", type=float, default=10.0, help="--normalize: clip_reward")
     ap.add_argument("--no-norm-reward", action="store_true", help="--normalize: observations only (norm_reward=False)")
@@ -102,8 +104,8 @@ def main(argv=None):
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if args.algo == "sac" and world > 1:
         ap.error("--algo sac runs one learner on one GPU (SB3's SAC has no data-parallel mode): launch it without torch.distributed")
-    if args.normalize and world > 1:
-        ap.error("--normalize keeps one set of running statistics: with several ranks they would diverge per rank (SB3 has no counterpart)")
+    if world > 1 and "RANK" not in os.environ:
+        ap.error("WORLD_SIZE=%d without RANK: several ranks are started by torch.distributed.run (see the module docstring)" % world)
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     if world > 1:
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
@@ -138,7 +140,8 @@ def main(argv=None):
     vn = None
     if args.normalize:
         from .vec_normalize import HipVecNormalize
-        env = vn = HipVecNormalize(env, norm_reward=not args.no_norm_reward, clip_obs=args.norm_clip_obs, clip_reward=args.norm_clip_reward)
+        env = vn = HipVecNormalize(env, norm_reward=not args.no_norm_reward, clip_obs=args.norm_clip_obs, clip_reward=args.norm_clip_reward,
+                                   sync_group="world" if world > 1 else None)
     ppo = PPO(env, net_arch=tuple(int(x) for x in args.arch.split(",")), n_steps=args.horizon,
               batch_size=args.minibatch, n_epochs=args.epochs, learning_rate=args.lr, seed=args.seed,
               buffer_dtype=torch.bfloat16 if args.bf16_buffer else torch.float32, rollout_graph=args.rollout_graph,
@@ -168,6 +171,8 @@ def main(argv=None):
     ppo.learn(args.total, log_interval=0 if args.json else 1, callback=_cb)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if vn is not None and vn.synced and args.save:
+        vn.sync()                                                       # every rank: the saved statistics are the agreed ones
     if rank == 0:
         if args.save:
             ppo.save(os.path.expanduser(args.save))
@@ -194,6 +199,7 @@ def main(argv=None):
                               "train_s_per_iter": trn, "overall_env_steps_per_s": per_it / (roll + trn),
                               "mean_reward_last": hist[-1]["mean_reward"], "wall_s": dt,
                               "grad_allreduce_calls": ppo.grad_sync.calls,
+                              "vecnorm_sync_calls": vn.sync_calls if vn is not None else 0,
                               "ep_rew_mean": hist[-1]["ep_rew_mean"], "ep_len_mean": hist[-1]["ep_len_mean"],
                               "explained_variance": hist[-1]["explained_variance"], "episodes": hist[-1]["episodes"],
                               "curve": [(h["timesteps"], h["ep_rew_mean"], h["ep_len_mean"]) for h in hist[::max(1, len(hist) // 200)]],

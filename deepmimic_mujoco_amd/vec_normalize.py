@@ -12,6 +12,13 @@ offers ``reset_tensor`` / ``step_tensor`` / ``num_envs`` / ``device`` / the two 
 tests/vecnorm_ref.py.  The flags ``training`` / ``norm_obs`` / ``norm_reward`` and the settings ``clip_obs`` / ``clip_reward`` /
 ``gamma`` / ``epsilon`` may be set between steps; a rollout graph captured earlier keeps the values it was captured with.
 
+``sync_group=`` (a ``torch.distributed`` group, or ``"world"`` for the default group, looked up at the first use) keeps ONE set of
+running statistics over the ranks of a data-parallel run: beside the running set a rank holds ``base``, what all
+ranks agreed on at the last ``sync()``, and ``acc``, what it alone has seen since; every step folds its batch into ``acc`` and
+normalises with merge(base, acc) (``dm_vecnorm_step_sync``, the same three launches), and ``sync()`` — two launches around one
+all-reduce of a [world, 2 D + 4] fp64 buffer, once per rollout in ``PPO`` — merges every rank's ``acc`` into ``base`` in rank order,
+after which the statistics are bit-identical on all ranks.  ``returns`` stays per rank.  Restated in tests/vecnorm_sync_ref.py.
+
 ``SAC(env, normalizer=HipVecNormalize(env))`` is the off-policy use (sac.py): the learner steps the inner env itself, feeds
 ``normalize_step_`` for the statistics and the actor's observation, stores raw transitions and normalises each sampled minibatch.
 """
@@ -52,8 +59,11 @@ class HipVecNormalize:
 
     _HIDDEN = ("step_sub", "sub_out")      # never forwarded: the wrapper steps all N envs at once
 
-    def __init__(self, venv, training=True, norm_obs=True, norm_reward=True, clip_obs=10.0, clip_reward=10.0, gamma=0.99, epsilon=1e-8):
+    def __init__(self, venv, training=True, norm_obs=True, norm_reward=True, clip_obs=10.0, clip_reward=10.0, gamma=0.99, epsilon=1e-8,
+                 sync_group=None):
         import torch
+        if isinstance(sync_group, str) and sync_group != "world":
+            raise ValueError("HipVecNormalize: sync_group is None, a torch.distributed group or \"world\", not %r" % (sync_group,))
         self._torch = t = torch
         self.venv = venv
         self.num_envs = N = int(venv.num_envs)
@@ -69,6 +79,11 @@ class HipVecNormalize:
         self._obs_mean, self._obs_var = self._state[:D], self._state[D:2 * D]
         self._obs_count, self._ret = self._state[2 * D:2 * D + 1], self._state[2 * D + 1:2 * D + 4]
         self.returns = t.zeros(N, dtype=t.float64, device=self.device)
+        # several ranks, one set of statistics: base | acc laid out like _state; the descriptor and the all-reduce buffer wait for the group
+        self._sync_group, self._sync, self._pg, self._gather, self.sync_calls = sync_group, None, None, None, 0
+        self._base = self._acc = None
+        if sync_group is not None:
+            self._base, self._acc = t.zeros_like(self._state), t.zeros_like(self._state)
         self._init_state()
         z = lambda *shape: t.zeros(*shape, device=self.device)
         self._own = dict(obs=z(N, D), rew=z(N), terminal_obs=z(N, D))
@@ -94,6 +109,90 @@ class HipVecNormalize:
         self._ret[1] = 1.0
         self._ret[2] = COUNT0
         self.returns.zero_()
+        self._rebase()
+
+    def _rebase(self):
+        """Synchronised object: the running statistics as they stand become ``base``, ``acc`` is emptied."""
+        if self._base is not None:
+            self._base.copy_(self._state)
+            self._acc.zero_()
+
+    @property
+    def synced(self):
+        return self._sync_group is not None
+
+    def _sync_world(self):
+        """(world, rank) of the sync group, resolved at the first use; ``"world"`` without an initialised process group is a world of
+        one.  Makes the all-reduce buffer and, on the GPU, the DmVecNormSync descriptor."""
+        if self._gather is None:
+            import torch.distributed as dist
+            g = self._sync_group
+            if isinstance(g, str):
+                g = dist.group.WORLD if dist.is_initialized() else None
+            self._pg = g
+            self._world, self._rank = (dist.get_world_size(g), dist.get_rank(g)) if g is not None else (1, 0)
+            self._gather = self._torch.zeros(self._world, self._state.numel(), dtype=self._torch.float64, device=self.device)
+            if self.on_gpu:
+                self._sync = _lib.DmVecNormSync(world=self._world, rank=self._rank, base=self._base.data_ptr(), acc=self._acc.data_ptr(),
+                                                gather=self._gather.data_ptr())
+        return self._world, self._rank
+
+    def _sets(self, flat):
+        """The two (mean, var, count) triples of views of a flat [2 D + 4] moment set: observations, returns."""
+        D = self.obs_dim
+        return (flat[:D], flat[D:2 * D], flat[2 * D:2 * D + 1]), (flat[2 * D + 1:2 * D + 2], flat[2 * D + 2:2 * D + 3], flat[2 * D + 3:2 * D + 4])
+
+    @staticmethod
+    def _merge_into(a, b):
+        """a <- merge(a, b) on (mean, var, count) views: ``update_from_moments`` with b as the batch (dm_vn_merge of
+        include/deepmimic_vecnorm.h on the torch path); a set of count 0 is skipped exactly."""
+        if float(b[2]) == 0.0:
+            return
+        if float(a[2]) == 0.0:
+            for x, y in zip(a, b):
+                x.copy_(y)
+            return
+        d, tot = b[0] - a[0], a[2] + b[2]
+        new_var = (a[1] * a[2] + b[1] * b[2] + d * d * a[2] * b[2] / tot) / tot
+        a[0].copy_(a[0] + d * b[2] / tot)
+        a[1].copy_(new_var)
+        a[2].copy_(tot)
+
+    def _rms_update_sync(self, which, x):
+        """The torch path of the synchronised update of set ``which`` (0 observations, 1 returns) with the rows x fp64 [n, ...]:
+        acc = merge(acc, batch), running = merge(base, acc)."""
+        t = self._torch
+        batch = (x.mean(0), x.var(0, unbiased=False), t.full((1,), float(x.shape[0]), dtype=t.float64))
+        acc, base, run = self._sets(self._acc)[which], self._sets(self._base)[which], self._sets(self._state)[which]
+        self._merge_into(acc, batch)
+        for r, b in zip(run, base):
+            r.copy_(b)
+        self._merge_into(run, acc)
+
+    def sync(self):
+        """Make the statistics of every rank of the sync group identical again: ``base`` = merge(base, every rank's ``acc`` in rank
+        order), ``acc`` emptied, running = base.  Pack launch, ONE all-reduce (sum; every rank fills its own row of a zeroed
+        [world, 2 D + 4] buffer, so the sum is a gather), merge launch: eager, on the current stream, never inside a captured graph."""
+        if not self.synced:
+            raise RuntimeError("HipVecNormalize.sync: built without a sync_group")
+        world, rank = self._sync_world()
+        if self.on_gpu:
+            self._call("dm_vecnorm_sync_pack", C.byref(self._sync))
+        else:
+            self._gather.zero_()
+            self._gather[rank].copy_(self._acc)
+        if self._pg is not None and world > 1:
+            import torch.distributed as dist
+            dist.all_reduce(self._gather, op=dist.ReduceOp.SUM, group=self._pg)
+        if self.on_gpu:
+            self._call("dm_vecnorm_sync_merge", C.byref(self._sync))
+        else:
+            for r in range(world):
+                for a, b in zip(self._sets(self._base), self._sets(self._gather[r])):
+                    self._merge_into(a, b)
+            self._acc.zero_()
+            self._state.copy_(self._base)
+        self.sync_calls += 1
 
     # ---- the three flags live in the descriptor the kernels read
     def _flag(name):
@@ -188,15 +287,25 @@ class HipVecNormalize:
             assert obs.shape == (self.num_envs, self.obs_dim) and rew.numel() == self.num_envs and done.numel() == self.num_envs
             if tobs is not None:
                 self._f32(tobs, "terminal_obs"), self._f32(tobs_out, "terminal_obs out")
-            self._call("dm_vecnorm_step", obs, rew, done, tobs, obs_out, rew_out, tobs_out)
+            if self.synced:
+                self._sync_world()
+                self._call("dm_vecnorm_step_sync", obs, rew, done, tobs, obs_out, rew_out, tobs_out, C.byref(self._sync))
+            else:
+                self._call("dm_vecnorm_step", obs, rew, done, tobs, obs_out, rew_out, tobs_out)
             return
         dn = done != 0
         if self.training and self.norm_obs:
-            self._rms_update(self._obs_mean, self._obs_var, self._obs_count, obs.double())
+            if self.synced:
+                self._rms_update_sync(0, obs.double())
+            else:
+                self._rms_update(self._obs_mean, self._obs_var, self._obs_count, obs.double())
         new_obs = self._norm_obs_t(obs)
         if self.training:
             self.returns.mul_(self.gamma).add_(rew.double())
-            self._rms_update(self._ret[0:1], self._ret[1:2], self._ret[2:3], self.returns[:, None])
+            if self.synced:
+                self._rms_update_sync(1, self.returns)
+            else:
+                self._rms_update(self._ret[0:1], self._ret[1:2], self._ret[2:3], self.returns[:, None])
         new_rew = self._norm_rew_t(rew)
         if tobs is not None:
             new_tobs = t.where(dn[:, None], self._norm_obs_t(tobs), tobs)
@@ -214,12 +323,18 @@ class HipVecNormalize:
     def reset_tensor(self, idx_init=None):
         obs = self.venv.reset_tensor() if idx_init is None else self.venv.reset_tensor(idx_init)
         self.out = dict(self._own, obs_raw=obs)
-        if self.on_gpu:
+        if self.on_gpu and self.synced:
+            self._sync_world()
+            self._call("dm_vecnorm_reset_sync", self._f32(obs, "obs"), self._own["obs"], C.byref(self._sync))
+        elif self.on_gpu:
             self._call("dm_vecnorm_reset", self._f32(obs, "obs"), self._own["obs"])
         else:
             self.returns.zero_()
             if self.training and self.norm_obs:
-                self._rms_update(self._obs_mean, self._obs_var, self._obs_count, obs.double())
+                if self.synced:
+                    self._rms_update_sync(0, obs.double())
+                else:
+                    self._rms_update(self._obs_mean, self._obs_var, self._obs_count, obs.double())
             self._own["obs"].copy_(self._norm_obs_t(obs))
         return self._own["obs"]
 
@@ -331,7 +446,8 @@ class HipVecNormalize:
 
     # ---- persistence
     def state_dict(self):
-        """numpy copies of the statistics and the settings (``returns`` included, so a resumed run continues bit for bit)."""
+        """numpy copies of the running statistics and the settings (``returns`` included, so a resumed run continues bit for bit).
+        The same keys with or without a sync group: a file of either kind of object loads into the other."""
         s = self._state.detach().cpu().numpy().copy()
         D = self.obs_dim
         return dict(obs_mean=s[:D], obs_var=s[D:2 * D], obs_count=s[2 * D:2 * D + 1], ret_mean=s[2 * D + 1:2 * D + 2],
@@ -347,6 +463,7 @@ class HipVecNormalize:
             raise ValueError("load_state_dict: statistics of %r columns for an env of %d" % (np.shape(sd["obs_mean"]), D))
         flat = np.concatenate([np.asarray(sd[k], np.float64).reshape(-1) for k in ("obs_mean", "obs_var", "obs_count", "ret_mean", "ret_var", "ret_count")])
         self._state.copy_(t.as_tensor(flat))
+        self._rebase()                       # a synchronised object: what was loaded is what the ranks agree on, nothing pending
         ret = np.asarray(sd.get("returns", ()), np.float64).reshape(-1)
         if ret.size == self.num_envs:
             self.returns.copy_(t.as_tensor(ret))
@@ -362,9 +479,9 @@ class HipVecNormalize:
             np.savez(f, **self.state_dict())
 
     @classmethod
-    def load(cls, path, venv):
+    def load(cls, path, venv, sync_group=None):
         with np.load(path, allow_pickle=False) as z:
             sd = {k: z[k] for k in z.files}
-        vn = cls(venv)
+        vn = cls(venv, sync_group=sync_group)
         vn.load_state_dict(sd)
         return vn

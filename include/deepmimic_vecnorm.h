@@ -54,9 +54,36 @@ int dm_vecnorm_reset(const DmVecNorm* vn, const float* obs, float* obs_out, void
  * touches neither returns nor scratch (both may be NULL here). */
 int dm_vecnorm_apply(const DmVecNorm* vn, int n, const float* obs, float* obs_out, const float* rew, float* rew_out, void* stream);
 
-/* All three return DM_VECNORM_EINVAL before any HIP call for a NULL struct or required pointer, N < 1, D < 1, n < 1, a scratch
- * smaller than dm_vecnorm_scratch_bytes(N, D), gamma outside [0, 1], epsilon < 0 or a clip <= 0 (NaN included); the reason is kept
- * per host thread. */
+/* ---- One set of running statistics over several ranks.  Beside the running statistics above, which the kernels go on
+ * reading, a rank keeps two more fp64 moment sets laid out obs mean [D] | obs var [D] | obs count | ret mean, var, count:
+ * `base`, what every rank agreed on at the last synchronisation (at the start RunningMeanStd's mean 0, var 1, count 1e-4), and
+ * `acc`, what this rank alone has seen since (empty: all zero).  Every merge of two sets is dm_vn_merge below: SB3's
+ * update_from_moments, with a set of count 0 skipped exactly. */
+typedef struct DmVecNormSync {
+    int32_t world, rank; /* ranks (>= 1), this rank in [0, world) */
+    double* base;        /* [2 D + 4] */
+    double* acc;         /* [2 D + 4] */
+    double* gather;      /* [world, 2 D + 4]: the buffer of the one all-reduce (sum) between sync_pack and sync_merge */
+} DmVecNormSync;
+
+/* dm_vecnorm_step / dm_vecnorm_reset with the statistics kept as above; same arguments and aliasing rules.  Training: the batch
+ * moments of the N rows (the same per-chunk launch), then acc = merge(acc, batch) and running = merge(base, acc), then the
+ * transform with `running`: three launches; one otherwise.  `base` is only read. */
+int dm_vecnorm_step_sync(const DmVecNorm* vn, const float* obs, const float* rew, const uint8_t* done, const float* tobs,
+                         float* obs_out, float* rew_out, float* tobs_out, const DmVecNormSync* sync, void* stream);
+int dm_vecnorm_reset_sync(const DmVecNorm* vn, const float* obs, float* obs_out, const DmVecNormSync* sync, void* stream);
+
+/* The two launches around the collective.  pack: row `rank` of gather = acc, every other row = 0, so that a sum over the ranks
+ * gathers (adding zeros is exact).  merge: base = merge(base, row 0, row 1, ..., row world - 1) in that order, acc = empty,
+ * running = base.  After it the 2 D + 4 doubles of `running` are bit-identical on every rank.  One launch each; of vn they read
+ * N (unused), D, device and the four statistics pointers. */
+int dm_vecnorm_sync_pack(const DmVecNorm* vn, const DmVecNormSync* sync, void* stream);
+int dm_vecnorm_sync_merge(const DmVecNorm* vn, const DmVecNormSync* sync, void* stream);
+
+/* All of them return DM_VECNORM_EINVAL before any HIP call for a NULL struct or required pointer, N < 1, D < 1, n < 1, a scratch
+ * smaller than dm_vecnorm_scratch_bytes(N, D), gamma outside [0, 1], epsilon < 0 or a clip <= 0 (NaN included), and the four
+ * entry points with a DmVecNormSync also for a NULL descriptor, a NULL pointer in it, world < 1 or rank outside [0, world); the
+ * reason is kept per host thread. */
 const char* dm_vecnorm_last_error(void);
 
 #ifdef __cplusplus
@@ -74,6 +101,25 @@ __device__ __forceinline__ float dm_vn_norm_one(double x, double mean, double sc
   return (float)y;
 }
 
+/* The ONE merge of two moment sets (mean, population variance, count), a <- merge(a, b): RunningMeanStd.update_from_moments with b
+ * as the batch.  A set of count 0 is skipped exactly: the other operand comes through bit for bit.  Not contracted into fused
+ * multiply-adds, so that every kernel that inlines it rounds alike. */
+__device__ __forceinline__ void dm_vn_merge(double& mean, double& var, double& count, double mb, double vb, double nb) {
+#pragma clang fp contract(off)
+  if (nb == 0.0) return;
+  if (count == 0.0) {
+    mean = mb;
+    var = vb;
+    count = nb;
+    return;
+  }
+  const double d = mb - mean, tot = count + nb;
+  const double new_var = (var * count + vb * nb + d * d * count * nb / tot) / tot;
+  mean = mean + d * nb / tot;
+  var = new_var;
+  count = tot;
+}
+
 /* Why the fields every entry point reads are refused, or NULL when they are fine (`returns` and `scratch` are not looked at). */
 static inline const char* dm_vn_struct_error(const DmVecNorm* v) {
   if (!v) return "null DmVecNorm";
@@ -83,6 +129,14 @@ static inline const char* dm_vn_struct_error(const DmVecNorm* v) {
   if (!(v->gamma >= 0.0 && v->gamma <= 1.0)) return "gamma outside [0, 1]";
   if (!(v->epsilon >= 0.0)) return "epsilon < 0";
   if (!(v->clip_obs > 0.0) || !(v->clip_reward > 0.0)) return "clip_obs or clip_reward <= 0";
+  return 0;
+}
+
+static inline const char* dm_vn_sync_error(const DmVecNormSync* y) {
+  if (!y) return "null DmVecNormSync";
+  if (y->world < 1) return "world < 1";
+  if (y->rank < 0 || y->rank >= y->world) return "rank outside [0, world)";
+  if (!y->base || !y->acc || !y->gather) return "null pointer in DmVecNormSync";
   return 0;
 }
 #endif
