@@ -44,6 +44,9 @@ VECNORM_EXPORTS = ["dm_vecnorm_scratch_bytes", "dm_vecnorm_step", "dm_vecnorm_re
                    "dm_vecnorm_step_sync", "dm_vecnorm_reset_sync", "dm_vecnorm_sync_pack", "dm_vecnorm_sync_merge"]
 # include/deepmimic_sac_norm.h (csrc/dm_sac.hip): SAC's minibatch gather with VecNormalize applied at sample time, SAC(normalizer=)
 SAC_NORM_EXPORTS = ["dm_sac_gather_norm"]
+# include/deepmimic_sac_nstep.h (csrc/dm_sac.hip): SAC's minibatch gather with n-step returns, SAC(n_steps=)
+SAC_NSTEP_EXPORTS = ["dm_sac_gather_nstep"]
+SAC_NSTEP_MAX = 64                                       # DM_SAC_NSTEP_MAX: one lane of a wave per step of the chain
 
 
 class DmVecNormSync(C.Structure):
@@ -238,6 +241,9 @@ def load_library():
     L.dm_vecnorm_last_error.restype = C.c_char_p
     L.dm_sac_gather_norm.argtypes = L.dm_sac_gather.argtypes[:-1] + [C.POINTER(DmVecNorm), vp]
     L.dm_sac_gather_norm.restype = C.c_int
+    # dm_sac_gather's arguments up to idx_out, then cap_steps, n_steps, gamma, k_out, the nullable DmVecNorm, the stream
+    L.dm_sac_gather_nstep.argtypes = L.dm_sac_gather.argtypes[:-1] + [i32, i32, f32, vp, C.POINTER(DmVecNorm), vp]
+    L.dm_sac_gather_nstep.restype = C.c_int
     for name in EXPORTS:
         if name not in ("dm_default_config", "dm_last_error"):
             getattr(L, name).restype = C.c_longlong if name in ("dm_policy_packed_floats", "dm_ppo_mlp_workspace_floats", "dm_ppo_wide_packed_elems", "dm_ppo_wide3_packed_elems", "dm_rollout_finish_workspace_bytes") else C.c_int

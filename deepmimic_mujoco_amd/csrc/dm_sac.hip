@@ -21,6 +21,7 @@
 #include <stdint.h>
 
 #include "../../include/deepmimic_sac_norm.h"
+#include "../../include/deepmimic_sac_nstep.h"
 #include "dm_launch.h"
 #include "dm_rng.h"
 
@@ -204,6 +205,70 @@ __global__ void sac_gather_norm_kernel(int B, int N, int D, int A, unsigned long
     rew[r] = v.norm_reward ? dm_vn_norm_one((double)x, 0.0, sqrt(v.ret_stats[1] + v.epsilon), v.clip_reward) : x;
     done[r] = r_done[i];
     if (idx_out) idx_out[r] = (int)i;
+  }
+}
+
+// ---- the n-step minibatch (include/deepmimic_sac_nstep.h; SB3 >= 2.7 NStepReplayBuffer): the draw, row i = (t, e), obs, act and the
+// five layouts of the two gathers above; the chain follows env e over the steps s_j = (t + j) mod cap, j < n, and stops after the first
+// j with done(s_j, e) = 1, s_j = newest (the row after it is unwritten, or the oldest one) or j = n - 1.  Which j reaches `newest` is
+// known from the ring state alone (dist), so lane j <= lim = min(n - 1, dist) loads (done, rew) of its step and no lane reads a row
+// past `newest`; one ballot finds the first stopping lane, one wave butterfly forms sum_j gamma^j r_j (lanes past the chain add -0,
+// the identity of fp32 addition: a chain of one keeps the stored reward's bits).  next_obs comes from the chain's last row and
+// done' = 1 - gamma^(k-1) (1 - done(last)), so that dm_sac_critic_loss's (1 - done) gamma is gamma^k (1 - done(last)); k = 1 gives done.
+// One wave per block (the ballot and the butterfly are the block's); one dependent level of loads after the ring state, not n.
+template <bool NORM>
+__global__ void __launch_bounds__(64) sac_gather_nstep_kernel(int B, int N, int D, int A, unsigned long long seed, const unsigned *counter,
+                                                              const unsigned *ring, const float *r_obs, const float *r_act,
+                                                              const float *r_rew, const float *r_done, const float *r_next, float *obs2,
+                                                              float *xq, float *xpi, float *xt, float *rew, float *done, int *idx_out,
+                                                              unsigned cap, int n, float gamma, int *k_out, SacNormArgs v) {
+  const int r = blockIdx.x;
+  if (r >= B) return;
+  // for every state dm_sac_store can write (pos < cap, fill <= cap) these are ring[0] and ring[1] themselves, and `total` and the draw
+  // are those of the two gathers above; the clamps only keep the chain arithmetic (dist < cap, rows < cap * N) inside the ring for a
+  // state written by hand, for which the "same draw" of the header is not promised
+  const unsigned pos = ring[0] % cap, fill = min(ring[1], cap);
+  const unsigned long long total = (unsigned long long)fill * (unsigned long long)N;
+  const unsigned h = dm_hash32(seed, (unsigned)r, counter[0], SAC_GATHER_TAG);
+  const size_t i = (size_t)(((unsigned long long)h * total) >> 32);        // < total, as in sac_gather_kernel
+  const unsigned t = (unsigned)(i / (size_t)N), e = (unsigned)(i - (size_t)t * N);
+  const unsigned newest = (pos + cap - 1u) % cap, dist = (newest + cap - t) % cap;   // t < fill <= cap; dist < cap
+  const int j = threadIdx.x, lim = min(n - 1, (int)dist);
+  float dn = 0.f, term = -0.f, pw = 1.f;
+  if (j <= lim) {
+    const size_t row = (size_t)((t + (unsigned)j) % cap) * N + e;
+    dn = r_done[row];
+    float x = r_rew[row];
+    if (NORM && v.norm_reward) x = dm_vn_norm_one((double)x, 0.0, sqrt(v.ret_stats[1] + v.epsilon), v.clip_reward);
+    for (int q = 0; q < j; q++) pw *= gamma;               // gamma^j by fp32 products: j roundings
+    term = pw * x;
+  }
+  const unsigned long long stop = __ballot(j <= lim && (dn != 0.f || j == lim));     // bit lim is set
+  const int k = __ffsll((long long)stop);                  // first stopping lane + 1
+  if (j >= k) term = -0.f;
+  for (int m = 32; m > 0; m >>= 1) term += __shfl_xor(term, m);
+  const float d_last = __shfl(dn, k - 1), pw_last = __shfl(pw, k - 1);
+  const size_t last = (size_t)((t + (unsigned)(k - 1)) % cap) * N + e;
+  const int K = D + A;
+  for (int c = threadIdx.x; c < D; c += blockDim.x) {
+    float o = r_obs[i * D + c], nx = r_next[last * D + c];
+    if (NORM && v.norm_obs) {
+      const double mean = v.obs_mean[c], scale = sqrt(v.obs_var[c] + v.epsilon);
+      o = dm_vn_norm_one((double)o, mean, scale, v.clip_obs);
+      nx = dm_vn_norm_one((double)nx, mean, scale, v.clip_obs);
+    }
+    obs2[(size_t)r * D + c] = o;
+    obs2[(size_t)(B + r) * D + c] = nx;
+    xq[(size_t)r * K + c] = o;
+    xpi[(size_t)r * K + c] = o;
+    xt[(size_t)r * K + c] = nx;
+  }
+  for (int c = threadIdx.x; c < A; c += blockDim.x) xq[(size_t)r * K + D + c] = r_act[i * A + c];
+  if (threadIdx.x == 0) {
+    rew[r] = term;
+    done[r] = 1.f - pw_last * (1.f - d_last);
+    if (idx_out) idx_out[r] = (int)i;
+    if (k_out) k_out[r] = k;
   }
 }
 
@@ -461,6 +526,23 @@ extern "C" int dm_sac_gather_norm(int B, int N, int D, int A, unsigned long long
                          vn->norm_obs != 0, vn->norm_reward != 0};
   hipLaunchKernelGGL(sac_gather_norm_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, B, N, D, A, seed, counter, ring, r_obs, r_act,
                      r_rew, r_done, r_next, obs2, xq, xpi, xt, rew, done, idx_out, v);
+  return dm_launch_status();
+}
+
+extern "C" int dm_sac_gather_nstep(int B, int N, int D, int A, unsigned long long seed, const unsigned *counter, const unsigned *ring,
+                                   const float *r_obs, const float *r_act, const float *r_rew, const float *r_done, const float *r_next,
+                                   float *obs2, float *xq, float *xpi, float *xt, float *rew, float *done, int *idx_out, int cap_steps,
+                                   int n_steps, float gamma, int *k_out, const DmVecNorm *vn, void *stream) {
+  if (B < 1 || N < 1 || D < 1 || A < 1 || !counter || !ring || !r_obs || !r_act || !r_rew || !r_done || !r_next || !obs2 || !xq ||
+      !xpi || !xt || !rew || !done)
+    return DM_EINVAL;
+  if (cap_steps < 1 || n_steps < 1 || n_steps > DM_SAC_NSTEP_MAX || !(gamma >= 0.f && gamma <= 1.f)) return DM_EINVAL;
+  if (vn && (dm_vn_struct_error(vn) || vn->D != D)) return DM_EINVAL;
+  SacNormArgs v = {};
+  if (vn) v = {vn->obs_mean, vn->obs_var, vn->ret_stats, vn->epsilon, vn->clip_obs, vn->clip_reward, vn->norm_obs != 0, vn->norm_reward != 0};
+  auto kernel = vn ? sac_gather_nstep_kernel<true> : sac_gather_nstep_kernel<false>;
+  hipLaunchKernelGGL(kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, B, N, D, A, seed, counter, ring, r_obs, r_act, r_rew, r_done,
+                     r_next, obs2, xq, xpi, xt, rew, done, idx_out, (unsigned)cap_steps, n_steps, gamma, k_out, v);
   return dm_launch_status();
 }
 

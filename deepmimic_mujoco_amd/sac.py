@@ -20,6 +20,12 @@ transitions (the raw terminal observation for a finished env) and each sampled m
 gradient step: ``dm_sac_gather_norm`` in the place of ``dm_sac_gather`` in the captured launch sequence, ``_norm_obs_t`` /
 ``_norm_rew_t`` in ``sample_torch``.  The learner steps the inner env itself; ``normalizer.training = False`` freezes the statistics
 and keeps both transforms.  DESIGN §25.
+
+``SAC(env, n_steps=n)`` is SB3's ``SAC(n_steps=)`` [EXT: NStepReplayBuffer, SB3 >= 2.7]: a sampled row keeps its observation and
+action, follows its env for up to n stored steps (stopping after a done, after the newest stored step, or after n), and carries the
+discounted reward sum, the chain's last next observation and ``done' = 1 - gamma^(k-1) (1 - done_last)``, which turns the one-step
+target's ``(1 - done) gamma`` into the n-step ``gamma^k (1 - done_last)``: nothing after the sample changes.  ``dm_sac_gather_nstep``
+(include/deepmimic_sac_nstep.h) in the place of either gather when n > 1, ``_sample_nstep_torch`` in ``sample_torch``.  DESIGN §27.
 """
 from __future__ import annotations
 
@@ -128,15 +134,18 @@ class SacPolicy:
 class SAC:
     def __init__(self, env, net_arch=(1024, 512), buffer_size=1_000_000, learning_starts=100, batch_size=256, tau=0.005, gamma=0.99,
                  train_freq=1, gradient_steps=1, ent_coef="auto", target_entropy="auto", learning_rate=3e-4, seed=0, device=None,
-                 fused=True, use_hip_graph=True, normalizer=None):
+                 fused=True, use_hip_graph=True, normalizer=None, n_steps=1):
         from .vec_normalize import HipVecNormalize
         if isinstance(env, HipVecNormalize):
             raise ValueError("SAC does not take a HipVecNormalize env: SB3 normalises at replay-sample time there, which this wrapper "
                              "does not do; pass the inner env")
         if normalizer is not None and not (isinstance(normalizer, HipVecNormalize) and normalizer.venv is env):
             raise ValueError("SAC(env, normalizer=...) takes a HipVecNormalize built on that same env (normalizer.venv is env)")
+        if not (isinstance(n_steps, (int, np.integer)) and not isinstance(n_steps, bool) and 1 <= n_steps <= _lib.SAC_NSTEP_MAX):
+            raise ValueError("SAC(n_steps=%r): an integer in 1 .. %d (one lane of the gather's wave per step)" % (n_steps, _lib.SAC_NSTEP_MAX))
         self.env = env
         self.normalizer = normalizer
+        self.n_steps = int(n_steps)                     # a hyperparameter fixed here: a captured graph holds it, a checkpoint does not
         self.device = torch.device(device) if device is not None else getattr(env, "device", torch.device("cpu"))
         if isinstance(self.device, int):
             self.device = torch.device("cuda", self.device)
@@ -317,9 +326,35 @@ class SAC:
         if idx is None:
             idx = torch.randint(0, self._fill * self.n_envs, (self.batch_size,), device=self.device, generator=self._gen)
         R, vn = self.ring, self.normalizer
+        if self.n_steps > 1:
+            return self._sample_nstep_torch(idx)
         b = dict(obs=R["obs"][idx], act=R["act"][idx], rew=R["rew"][idx], next_obs=R["next_obs"][idx], done=R["done"][idx])
         if vn is not None:
             b.update(obs=vn._norm_obs_t(b["obs"]), next_obs=vn._norm_obs_t(b["next_obs"]), rew=vn._norm_rew_t(b["rew"]))
+        return b
+
+    def _sample_nstep_torch(self, idx):
+        """The n-step minibatch of ring rows ``idx`` with torch ops (include/deepmimic_sac_nstep.h states the semantics): row i =
+        (t, e) is followed over the steps (t + j) mod cap, j <= lim = min(n - 1, distance of t to the newest stored step), up to and
+        including the first done; rewards are normalised one by one, then discounted; ``k`` is the number of rows used."""
+        R, vn, N, cap, n, dev = self.ring, self.normalizer, self.n_envs, self.cap_steps, self.n_steps, self.device
+        pos = int(self.ring_state[0])
+        idx = torch.as_tensor(idx, device=dev).long()
+        t, e = idx // N, idx % N
+        j = torch.arange(n, device=dev)
+        lim = torch.clamp((pos + cap - 1 - t) % cap, max=n - 1)[:, None]
+        rows = torch.where(j <= lim, ((t[:, None] + j) % cap) * N + e[:, None], idx[:, None])      # past lim: never used
+        stop = ((R["done"][rows] != 0) | (j == lim)) & (j <= lim)
+        used = (stop.cumsum(1) - stop.long()) == 0          # up to and including the first stop
+        k = used.sum(1)
+        last = rows.gather(1, (k - 1)[:, None])[:, 0]
+        r = R["rew"][rows] if vn is None else vn._norm_rew_t(R["rew"][rows])
+        g = torch.full((n,), self.gamma, dtype=torch.float32, device=dev)
+        pw = torch.cat([torch.ones(1, device=dev), g[:-1].cumprod(0)])     # gamma^j by fp32 products
+        b = dict(obs=R["obs"][idx], act=R["act"][idx], rew=torch.where(used, pw * r, torch.zeros_like(r)).sum(1),
+                 next_obs=R["next_obs"][last], done=1.0 - pw[k - 1] * (1.0 - R["done"][last]), k=k)
+        if vn is not None:
+            b.update(obs=vn._norm_obs_t(b["obs"]), next_obs=vn._norm_obs_t(b["next_obs"]))
         return b
 
     def gradient_step_torch(self, batch=None, eps_pi=None, eps_next=None):
@@ -373,7 +408,7 @@ class SAC:
             B, D, A, K, H1, H2, dev = self.batch_size, self.obs_dim, self.act_dim, self.K, self.H1, self.H2, self.device
             z = lambda *s: torch.zeros(*s, device=dev)
             self._fb = dict(obs2=z(2 * B, D), xq=z(B, K), xpi=z(B, K), xt=z(B, K), rew=z(B), done=z(B),
-                            idx=torch.zeros(B, dtype=torch.int32, device=dev),
+                            idx=torch.zeros(B, dtype=torch.int32, device=dev), k=torch.zeros(B, dtype=torch.int32, device=dev),
                             h1a=z(2 * B, H1), h2a=z(2 * B, H2), head=z(2 * B, 2 * A), logp=z(2 * B),
                             h1t=z(2, B, H1), h2t=z(2, B, H2), qt=z(2, B, 1), h1q=z(2, B, H1), h2q=z(2, B, H2), q=z(2, B, 1),
                             dq=z(2, B), dh2=z(2, B, H2), dh1=z(2, B, H1),
@@ -399,7 +434,10 @@ class SAC:
         # 1. minibatch; with a normaliser the same rows, normalised inside the launch with the statistics it finds when it runs
         gather = (B, self.n_envs, D, A, seed, ctr, self.ring_state, R["obs"], R["act"], R["rew"], R["done"], R["next_obs"],
                   fb["obs2"], fb["xq"], fb["xpi"], fb["xt"], fb["rew"], fb["done"], fb["idx"])
-        if self.normalizer is None:
+        if self.n_steps > 1:                   # the n-step chain of every drawn row, in the same one launch
+            call("dm_sac_gather_nstep", *gather, self.cap_steps, self.n_steps, self.gamma, fb["k"],
+                 None if self.normalizer is None else ctypes.byref(self.normalizer._desc))
+        elif self.normalizer is None:
             call("dm_sac_gather", *gather)
         else:
             call("dm_sac_gather_norm", *gather, ctypes.byref(self.normalizer._desc))

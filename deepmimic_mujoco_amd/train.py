@@ -22,6 +22,8 @@ def build_parser():
     ap.add_argument("--buffer-size", type=int, default=5_000_000, help="--algo sac: replay transitions (src/sac_sb3.py)")
     ap.add_argument("--learning-starts", type=int, default=100, help="--algo sac: uniform-action env steps before learning")
     ap.add_argument("--gradient-steps", type=int, default=1, help="--algo sac: gradient steps per vec-env step")
+    ap.add_argument("--n-step", type=int, default=1,
+                    help="--algo sac: n-step returns, SB3's SAC(n_steps=): 1 .. 64, gathered on the device inside the sample launch")
     ap.add_argument("--motion", default="walk", help="clip name or comma list (multi-clip: env i -> clip i mod k)")
     ap.add_argument("--env", default="deep_mimic_mujoco", choices=["deep_mimic_mujoco", "dp_combined_env"],
                     help="env_name of src/sb3_ppo.py:247-248 (dp_combined_env: walk/run/getup state machine on humanoid3d)")
@@ -100,6 +102,8 @@ def main(argv=None):
         ap.error("--bf16-learner and --bf16x3-learner are mutually exclusive")
     if args.eval_envs < 0:
         ap.error("--eval-envs must be >= 0")
+    if not 1 <= args.n_step <= 64 or (args.n_step != 1 and args.algo != "sac"):
+        ap.error("--n-step takes 1 .. 64 and belongs to --algo sac")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if args.algo == "sac" and world > 1:
@@ -220,7 +224,7 @@ def _train_sac(args, env, motions, local_rank):
         from .vec_normalize import HipVecNormalize
         vn = HipVecNormalize(env, norm_reward=not args.no_norm_reward, clip_obs=args.norm_clip_obs, clip_reward=args.norm_clip_reward)
     sac = SAC(env, net_arch=tuple(int(x) for x in args.arch.split(",")), buffer_size=args.buffer_size,
-              learning_starts=args.learning_starts, gradient_steps=args.gradient_steps, seed=args.seed, normalizer=vn)
+              learning_starts=args.learning_starts, gradient_steps=args.gradient_steps, seed=args.seed, normalizer=vn, n_steps=args.n_step)
     hist = []
     dash = None
     batch_env = _eval_batch_env(args, motions, local_rank) if args.eval_envs > 0 else None
@@ -264,7 +268,7 @@ def _train_sac(args, env, motions, local_rank):
     if args.json:
         last = hist[-1] if hist else {}
         print(json.dumps({"workload": "sac", "integrator": args.integrator, "envs": env.num_envs, "arch": args.arch, "buffer_size": args.buffer_size,
-                          "gradient_steps": args.gradient_steps, "normalize": vn is not None, "total_timesteps": sac.num_timesteps, "n_updates": sac._n_updates,
+                          "gradient_steps": args.gradient_steps, "n_steps": sac.n_steps, "normalize": vn is not None, "total_timesteps": sac.num_timesteps, "n_updates": sac._n_updates,
                           "env_steps_per_s": sac.num_timesteps / dt, "wall_s": dt,
                           "ep_rew_mean": last.get("ep_rew_mean"), "ep_len_mean": last.get("ep_len_mean"),
                           "critic_loss": last.get("critic_loss"), "actor_loss": last.get("actor_loss"), "ent_coef": last.get("ent_coef"),
